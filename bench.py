@@ -23,11 +23,21 @@ A failed RCCL initialisation is an error exit, never a fallback.  After the time
 down and rank 0 ALONE produces `cpu_baseline`, `rel_err_vs_oracle` and `secondary` (no rank waits in a collective
 while rank 0 spends its seconds on the CPU), for every N.
 
-Prints ONE JSON line (rank 0).  `roofline`/`kernels` come from HIP events recorded on the launch stream between the
-passes of the same K iterations run once more on ONE stream right after the timed region (under overlap a kernel's
-duration is a property of the interleaving; with --no-overlap the timed region itself carries the events).
-`cpu_baseline` is the CPU oracle (a C port of the reference's algorithm, oracle/aoc_oracle.c) timed on this host on a
-bounded sample, `rel_err_vs_oracle` the GPU's iterates against the oracle's on that same sample.
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs and nothing else: it sets up (including the
+allocation autotuning), warms up, times the K steps and prints `metric`, `value`, `unit`, `ms_per_step`, `dtype`, ...
+with the configuration, the placement measurements and the shard's summary.  Everything else moves behind --full:
+`ms_per_step_first_allocated`, `steps10`, `roofline`/`kernels`, the collective's own latency, `cpu_baseline`,
+`rel_err`, `rel_err_vs_oracle` and `secondary` (--no-cpu-baseline / --no-secondary drop parts of that record again).
+Under --full, `roofline`/`kernels` come from HIP events recorded on the launch stream between the passes of the same K
+iterations run once more on ONE stream right after the timed region (under overlap a kernel's duration is a property
+of the interleaving; with --no-overlap the timed region itself carries the events).  `cpu_baseline` is the CPU oracle
+(a C port of the reference's algorithm, oracle/aoc_oracle.c) timed on this host on a bounded sample,
+`rel_err_vs_oracle` the GPU's iterates against the oracle's on that same sample.
+
+--dump-outputs DIR writes what the timed path handed its caller after the last timed step (rank 0's shard) as float64
+.npy files, about 40 MB at the default size; diverged trajectories are flagged by a mask and written as 0, so that
+every value is finite (dump_outputs).  The inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -69,16 +79,24 @@ def parse():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong scaling: total trajectories over all ranks (per rank = this / N); 0 = weak scaling with --batch-per-gpu")
     ap.add_argument("--cpu-budget-s", type=float, default=15.0,
-                    help="wall seconds of the multi-threaded CPU baseline sample (the 1-thread sample gets a third)")
+                    help="wall seconds of the multi-threaded CPU baseline sample (the 1-thread sample gets a third; --full)")
     ap.add_argument("--horizon", type=int, default=500)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the small configs reported beside the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the oracle comparison")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the small configs reported beside the headline")
     ap.add_argument("--no-overlap", action="store_true",
                     help="one stream; the timed region itself carries the per-pass HIP events")
     ap.add_argument("--placement-candidates", type=int, default=7,
                     help="allocation autotuning before the run: build this many solvers, keep the fastest (batch.best_placed); "
                          "1 = take the buffers as first allocated")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="the whole record beside the headline: first-allocated and 10-iteration figures, per-kernel "
+                         "attribution and roofline, the collective's latency, CPU baseline, oracle comparison, secondary configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs after its last step as DIR/<name>.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def launch_ranks(a):
@@ -501,6 +519,91 @@ def vector_issue(dom, units, T):
     return None
 
 
+# --dump-outputs: the states and inputs of a seeded sample of trajectories (this many trajectory-stages: 8 fp64 values
+# each, ~33 MB) and the per-trajectory scalars of up to this many trajectories (6 fp64 values each, ~13 MB)
+DUMP_STAGES = 1024 * 500
+DUMP_SCALARS = 1 << 18
+
+
+def _sample(B, n, seed):
+    """all of 0..B-1 when n >= B, else n of them drawn without replacement by a fixed seed, sorted"""
+    if n >= B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(seed).choice(B, n, replace=False))
+
+
+def _finite_rows(arrays):
+    """per trajectory (first axis): every value of every array finite"""
+    ok = np.ones(len(arrays[0]), bool)
+    for v in arrays:
+        ok &= np.isfinite(v.reshape(len(v), -1)).all(1)
+    return ok
+
+
+def dump_outputs(d, res, sc, summ, T):
+    """What a caller of the timed path receives after its last step: res.current() (states xx (B,6,T), inputs uu
+    (B,2,T)) for a seeded sample of trajectories, res.scalars() (cost, cost_new, descent, stepsize, ntrials, status) of
+    every trajectory up to DUMP_SCALARS (else of a seeded sample), and the reduced summary the timed region ends with.
+    The indices of the samples are written beside them (`sample_index`, `scalars_index`).  Everything as float64.
+    Trajectories that diverged (from kk = 9 a few per cent of the random starts, in the oracle as on the device) are
+    counted, not written — the convention of the summary (sharding.local_summary): `finite` / `sample_finite` are 1 for a
+    trajectory whose scalars / states and inputs are all finite and 0 otherwise, and the values of a 0 are written as
+    0, so that every file is finite and two builds compare both the set of diverged trajectories and the values."""
+    os.makedirs(d, exist_ok=True)
+    xx, uu = res.current()
+    B = xx.shape[0]
+    ti = _sample(B, max(DUMP_STAGES // T, 1), 20260405)
+    si = _sample(B, DUMP_SCALARS, 20260406)
+    sample = {"xx_sample": xx[ti].astype(np.float64), "uu_sample": uu[ti].astype(np.float64)}
+    scalars = {k: v[si].astype(np.float64) for k, v in sc.items()}
+    arrays = {"sample_index": ti, "scalars_index": si, "summary": summ.cpu().numpy()}
+    for group, mask in ((sample, "sample_finite"), (scalars, "finite")):
+        ok = _finite_rows(list(group.values()))
+        for v in group.values():
+            v[~ok] = 0.0
+        arrays.update(group)
+        arrays[mask] = ok
+    for name, v in arrays.items():
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        assert np.isfinite(v).all(), name
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
+def attribution(batch, prm, evs, full, nt, Bg, T, K):
+    """--full: per-pass durations from the HIP events of a one-stream run of the K iterations (this rank), by Hessian
+    regime (`full`: the full-Hessian iterations) -> (ms [K][pass], `kernels` entries, the dominant entry)."""
+    units = Bg * T                              # trajectory-stages one launch processes
+    passes = batch.NewtonBatchSolver.PASSES
+    ms = np.array([[ev[i].elapsed_time(ev[i + 1]) for i in range(len(passes))] for ev in evs])   # [K][pass]
+    tp = os.path.join(ROOT, "profiles", "traffic.json")
+    tj = json.load(open(tp)) if os.path.exists(tp) else {}
+    same_run = tj.get("batch_per_gpu") == Bg and tj.get("T") == T and tj.get("steps") == K
+    def entry(pname, names, pick, which):
+        avg = float(ms[pick, passes.index(pname)].mean())
+        e = {"pass": pname, "kernel": names[pname], "iterations": which, "launches": int(pick.sum()), "avg_ms": avg}
+        if pname in BYTES:
+            alg, sto = BYTES[pname]
+            if pname == "forward" and ", 2, true, float>" in names[pname]:
+                sto -= 24          # the nominal states are re-computed, not read (float32: 6 x 4 B)
+            e.update(algorithmic_bytes=alg * units, stored_bytes=sto * units,
+                     algorithmic_GBps=alg * units / avg / 1e6, stored_GBps=sto * units / avg / 1e6,
+                     frac_algorithmic=alg * units / avg / 1e6 / HBM_PEAK_GBS, frac_stored=sto * units / avg / 1e6 / HBM_PEAK_GBS,
+                     traffic=tj.get("kernels", {}).get(names[pname], {}).get("hbm_bytes_per_launch") if same_run else None)
+        return e
+
+    kernels = []
+    if (~full).any():
+        kernels.append(entry("backward", kernel_names(nt, False), ~full, "Gauss-Newton, kk <= %d" % prm.hessian_switch))
+    if full.any():
+        kernels.append(entry("backward", kernel_names(nt, True), full, "full Hessian, kk > %d" % prm.hessian_switch))
+    for pname in passes[1:]:   # the other passes do not change with the Hessian
+        kernels.append(entry(pname, kernel_names(nt, False), np.ones(K, bool), "all"))
+    # the dominant kernel: the one the iterations spend most time in (launches x average; by average alone the entry flipped
+    # between the forward pass and the 11-launch full-Hessian backward pass from box to box, 1.79 against 1.77-1.81 ms)
+    dom = max((e for e in kernels if "algorithmic_bytes" in e), key=lambda e: e["avg_ms"] * e["launches"])
+    return ms, kernels, dom
+
+
 def run(a):
     import torch
     import torch.distributed as dist
@@ -556,13 +659,20 @@ def run(a):
     # test hook (the 2-rank rehearsal): rank r takes candidate r instead of the fastest, so that the ranks' choices DIFFER
     # and every branch that depends on a rank's own choice is taken differently by the ranks
     force = rank if os.environ.get("AOC_BENCH_FORCE_CHOICE", "0") == "1" else None
-    # one stream: the attribution pass (per-kernel durations behind `roofline` / `kernels`), or everything with --no-overlap;
-    # its allocation is chosen like the headline's (the write-heavy passes differ by 10-20 % between allocations)
+    # one stream: the attribution pass (per-kernel durations behind `roofline` / `kernels`, --full), or everything when the
+    # batch is not split over two streams; its allocation is chosen like the headline's (the write-heavy passes differ by
+    # 10-20 % between allocations).  keep_first: the first-allocated solver is timed too (--full).
     n1 = ncand if big else 1
-    s, placement["one_stream_solver"] = batch.best_placed(lambda: batch.NewtonBatchSolver(bp, Bg, prm), x0d, min(n1, fits()),
-                                                          keep_first=a.no_overlap, force=force)
+
+    def one_stream():
+        return batch.best_placed(lambda: batch.NewtonBatchSolver(bp, Bg, prm), x0d, min(n1, fits()),
+                                 keep_first=a.full and a.no_overlap, force=force)
     # two half batches on two streams pay while each half is still a large-batch launch (one wavefront per tile kernels)
-    overlap = not a.no_overlap and s.nt >= 2048 and fits() >= 1 and torch.cuda.mem_get_info(dev)[0] / share > 1.1 * per_solver
+    can_overlap = not a.no_overlap and batch.ntiles(Bg) >= 2048
+    s = None
+    if a.full or not can_overlap:
+        s, placement["one_stream_solver"] = one_stream()
+    overlap = can_overlap and fits() >= 1 and torch.cuda.mem_get_info(dev)[0] / share > 1.1 * per_solver
     if world > 1:   # the timed regions hold collectives: every rank must take the same arrangement (free memory is a
         #             per-rank observation — ranks rehearsing on one device see each other's transient allocations)
         flag = torch.tensor([1.0 if overlap else 0.0], dtype=torch.float64, device=dev)
@@ -570,10 +680,13 @@ def run(a):
     s2 = None
     if overlap:
         s2, placement["two_stream_solver"] = batch.best_placed(lambda: batch.TwoStreamNewtonSolver(bp, Bg, prm), x0d,
-                                                               min(ncand, fits()), keep_first=True, force=force)
+                                                               min(ncand, fits()), keep_first=a.full, force=force)
+    elif s is None:     # a plain run whose batch does not go on two streams after all: the one-stream solver is timed
+        s, placement["one_stream_solver"] = one_stream()
     # the solver a caller who does not choose its allocation gets: candidate 0 of the kind that is timed
     sv_first = placement["two_stream_solver" if overlap else "one_stream_solver"].pop("first", None)
-    placement["one_stream_solver"].pop("first", None)
+    if s is not None:
+        placement["one_stream_solver"].pop("first", None)
 
     def barrier():
         torch.cuda.synchronize(dev)
@@ -602,7 +715,7 @@ def run(a):
     # warmup: W iterations from the initial guess (and one summary, so that no lazily loaded code object is first
     # touched inside the timed region), then reset: the timed region is exactly iterations 0..K-1 of the solve
     res = s2 if overlap else s
-    warm = [s2, s] if overlap else [s]
+    warm = [sv for sv in (s2, s) if sv is not None]
     for sv in warm:
         sv.set_initial_from_x0(x0d)
         for k in range(a.warmup):
@@ -613,26 +726,29 @@ def run(a):
         for k in range(a.warmup):
             sv_first.iterate(k)
         sv_first.summary()
-    s.iterate_timed(0)
+    if s is not None:
+        s.iterate_timed(0)
     if overlap:
         el, every, summ, _ = timed_region(s2, lambda k: s2.iterate(k))
-        _, _, _, evs = timed_region(s, lambda k: s.iterate_timed(k))      # attribution: same iterations, one stream
+        if a.full:
+            _, _, _, evs = timed_region(s, lambda k: s.iterate_timed(k))      # attribution: same iterations, one stream
     else:
         el, every, summ, evs = timed_region(s, lambda k: s.iterate_timed(k))
-    # the same K iterations on the allocation as FIRST made (what a caller of the API gets without best_placed)
-    # (timed_region holds collectives: every rank must take the same branch, whatever ITS choice was — a rank whose chosen
-    # candidate is its first one times it once more)
-    if placement["candidates"] <= 1:
-        el_first = el
-    else:
-        sv1 = res if (sv_first is None or sv_first is res) else sv_first
-        el_first = timed_region(sv1, lambda k: sv1.iterate(k))[0]
-        del sv1
+    if a.full:
+        # the same K iterations on the allocation as FIRST made (what a caller of the API gets without best_placed)
+        # (timed_region holds collectives: every rank must take the same branch, whatever ITS choice was — a rank whose
+        # chosen candidate is its first one times it once more)
+        if placement["candidates"] <= 1:
+            el_first = el
+        else:
+            sv1 = res if (sv_first is None or sv_first is res) else sv_first
+            el_first = timed_region(sv1, lambda k: sv1.iterate(k))[0]
+            del sv1
+        # SURVEY 8d config 4 is quoted on 10 fixed iterations: the same solver over kk = 0..9 (no full-Hessian storms yet)
+        el10 = el if K == 10 else timed_region(res, lambda k: res.iterate(k), 10)[0]
+        if K != 10:          # leave the K-iteration results in place for what follows
+            timed_region(res, lambda k: res.iterate(k))
     del sv_first
-    # SURVEY 8d config 4 is quoted on 10 fixed iterations: the same solver over kk = 0..9 (no full-Hessian storms yet)
-    el10 = el if K == 10 else timed_region(res, lambda k: res.iterate(k), 10)[0]
-    if K != 10:          # leave the K-iteration results in place for what follows
-        timed_region(res, lambda k: res.iterate(k))
     # every rank's draw: [chosen probe ms, first-candidate probe ms] per rank (zeros where nothing was probed)
     pk = placement["two_stream_solver" if overlap else "one_stream_solver"]
     mine = torch.zeros(world, 2, dtype=torch.float64, device=dev)
@@ -644,61 +760,37 @@ def run(a):
     placement["per_rank_chosen"] = [int(v) for v in sharding.all_reduce(chose, "sum").cpu().numpy()]
     sc = res.scalars()
     coll = None
-    if world > 1:   # the path's one collective by itself, outside the headline region
+    if world > 1:   # what the path's one collective ran on; --full: the collective by itself, outside the headline region
         vec = res.summary()
-        ts = []
-        for _ in range(12):
-            barrier()
-            t0 = time.perf_counter()
-            sharding.reduce_summary(vec.clone())
-            torch.cuda.synchronize(dev)
-            ts.append(time.perf_counter() - t0)
-        ts = ts[2:]
         coll = {"backend": dist.get_backend(), "world_seen": int(dist.get_world_size()), "payload_bytes": int(vec.numel() * 8),
-                "what": "all_reduce(sum) of %d fp64 scalars on a device tensor, incl. the synchronisation after it" % vec.numel(),
-                "us": float(np.mean(ts) * 1e6), "us_min": float(np.min(ts) * 1e6), "repeats": len(ts),
                 "device_per_rank": "cuda:0 for every rank (one-GPU rehearsal)" if one_dev else "cuda:LOCAL_RANK"}
+        if a.full:
+            ts = []
+            for _ in range(12):
+                barrier()
+                t0 = time.perf_counter()
+                sharding.reduce_summary(vec.clone())
+                torch.cuda.synchronize(dev)
+                ts.append(time.perf_counter() - t0)
+            ts = ts[2:]
+            coll.update(what="all_reduce(sum) of %d fp64 scalars on a device tensor, incl. the synchronisation after it" % vec.numel(),
+                        us=float(np.mean(ts) * 1e6), us_min=float(np.min(ts) * 1e6), repeats=len(ts))
     if os.environ.get("AOC_BENCH_DUMP"):   # tests: this rank's per-trajectory results after the K iterations
         full = {} if os.environ.get("AOC_BENCH_DUMP_LIGHT") == "1" else dict(zip(("xx", "uu"), res.current()))   # light: scalars only
         np.savez(os.path.join(os.environ["AOC_BENCH_DUMP"], "rank%d_of_%d.npz" % (rank, world)), first=first,
                  summary=summ.cpu().numpy(), **full, **sc)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res, sc, summ, T)
     if world > 1:   # nothing below talks to another rank: rank 0 alone finishes the record
         barrier()
         dist.destroy_process_group()
     if rank != 0:
         return
 
-    # per-pass durations from the HIP events (this rank), by Hessian regime: Gauss-Newton for kk <= 8, full after
-    passes = batch.NewtonBatchSolver.PASSES
-    ms = np.array([[ev[i].elapsed_time(ev[i + 1]) for i in range(len(passes))] for ev in evs])   # [K][pass]
-    full = np.arange(K) > prm.hessian_switch
+    full = np.arange(K) > prm.hessian_switch    # Hessian regime of each timed iteration: Gauss-Newton for kk <= 8, full after
     units = Bg * T                              # trajectory-stages one launch processes
-    tp = os.path.join(ROOT, "profiles", "traffic.json")
-    tj = json.load(open(tp)) if os.path.exists(tp) else {}
-    same_run = tj.get("batch_per_gpu") == Bg and tj.get("T") == T and tj.get("steps") == K
-    def entry(pname, names, pick, which):
-        avg = float(ms[pick, passes.index(pname)].mean())
-        e = {"pass": pname, "kernel": names[pname], "iterations": which, "launches": int(pick.sum()), "avg_ms": avg}
-        if pname in BYTES:
-            alg, sto = BYTES[pname]
-            if pname == "forward" and ", 2, true, float>" in names[pname]:
-                sto -= 24          # the nominal states are re-computed, not read (float32: 6 x 4 B)
-            e.update(algorithmic_bytes=alg * units, stored_bytes=sto * units,
-                     algorithmic_GBps=alg * units / avg / 1e6, stored_GBps=sto * units / avg / 1e6,
-                     frac_algorithmic=alg * units / avg / 1e6 / HBM_PEAK_GBS, frac_stored=sto * units / avg / 1e6 / HBM_PEAK_GBS,
-                     traffic=tj.get("kernels", {}).get(names[pname], {}).get("hbm_bytes_per_launch") if same_run else None)
-        return e
-
-    kernels = []
-    if (~full).any():
-        kernels.append(entry("backward", kernel_names(s.nt, False), ~full, "Gauss-Newton, kk <= %d" % prm.hessian_switch))
-    if full.any():
-        kernels.append(entry("backward", kernel_names(s.nt, True), full, "full Hessian, kk > %d" % prm.hessian_switch))
-    for pname in passes[1:]:   # the other passes do not change with the Hessian
-        kernels.append(entry(pname, kernel_names(s.nt, False), np.ones(K, bool), "all"))
-    # the dominant kernel: the one the iterations spend most time in (launches x average; by average alone the entry flipped
-    # between the forward pass and the 11-launch full-Hessian backward pass from box to box, 1.79 against 1.77-1.81 ms)
-    dom = max((e for e in kernels if "algorithmic_bytes" in e), key=lambda e: e["avg_ms"] * e["launches"])
+    if a.full:
+        ms, kernels, dom = attribution(batch, prm, evs, full, s.nt, Bg, T, K)
     fin_b = int(summ[3].item() - summ[4].item())
     out = {
         "metric": "Newton iters/sec (whole node), batched 6-state T=%d trajectories; fp64 rel-err" % T,
@@ -706,12 +798,16 @@ def run(a):
         "unit": "trajectory-Newton-iterations/s",
         "n_gpus": world, "steps": K, "warmup": a.warmup,
         "ms_per_step": el / K * 1e3,
-        # the same K iterations on the allocation as first made, i.e. without batch.best_placed (DESIGN.md section 4 "placement")
-        "ms_per_step_first_allocated": el_first / K * 1e3,
-        "value_first_allocated": Bg * world * K / el_first,
-        "steps10": {"workload": "the same solver over kk = 0..9 only (SURVEY 8d config 4: \"10 fixed iterations\")",
-                    "ms_per_step": el10 / 10 * 1e3, "value": Bg * world * 10 / el10,
-                    "iteration_hbm_frac_per_gpu": ITERATION_BYTES * Bg * T * 10 / el10 / 1e9 / HBM_PEAK_GBS},
+    }
+    if a.full:
+        out.update({
+            # the same K iterations on the allocation as first made, i.e. without batch.best_placed (DESIGN.md section 4 "placement")
+            "ms_per_step_first_allocated": el_first / K * 1e3,
+            "value_first_allocated": Bg * world * K / el_first,
+            "steps10": {"workload": "the same solver over kk = 0..9 only (SURVEY 8d config 4: \"10 fixed iterations\")",
+                        "ms_per_step": el10 / 10 * 1e3, "value": Bg * world * 10 / el10,
+                        "iteration_hbm_frac_per_gpu": ITERATION_BYTES * Bg * T * 10 / el10 / 1e9 / HBM_PEAK_GBS}})
+    out.update({
         "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
         "dtype": "f64", "data": "synthetic",
         "config": {"workload": "BASELINE configs[3]: step-maneuver, T=%d (tf=1, dt=%g), fp64, random x0 by global index, "
@@ -721,18 +817,21 @@ def run(a):
                                % (T, pr.dt, Bg, Bg * world, world, "" if world == 1 else "s", K - 1, int((~full).sum()), int(full.sum())),
                    "batch_per_gpu": Bg, "global_batch": Bg * world, "T": T, "parallelism": "batch-sharded x%d" % world,
                    "streams": "two half batches on two HIP streams (batch.TwoStreamNewtonSolver)" if overlap else "one",
-                   "armijo": {"stepsize_0": 1.0, "cc": 0.5, "beta": 0.7, "maxiters": 10}},
-        "roofline": {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["algorithmic_GBps"], "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": dom["frac_algorithmic"], "traffic": dom["traffic"],
-                     "algorithmic_bytes_per_launch": dom["algorithmic_bytes"], "stored_bytes_per_launch": dom["stored_bytes"],
-                     "frac_stored": dom["frac_stored"], "avg_launch_ms": dom["avg_ms"], "launches": dom["launches"],
-                     "measured_in": ("one-stream repeat of the same %d iterations right after the timed region" % K)
-                     if overlap else "the timed region",
-                     # the same kernel against the other roof it touches: vector instructions per wavefront-stage from
-                     # the SQ counters of the committed one-stream run, priced at the nominal issue rate
-                     "vector_issue": vector_issue(dom, units, T)},
-        "kernels": kernels,
-        "attribution_ms_per_step": float(ms.sum(1).mean()),
+                   "armijo": {"stepsize_0": 1.0, "cc": 0.5, "beta": 0.7, "maxiters": 10}}})
+    if a.full:
+        out.update({
+            "roofline": {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["algorithmic_GBps"], "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": dom["frac_algorithmic"], "traffic": dom["traffic"],
+                         "algorithmic_bytes_per_launch": dom["algorithmic_bytes"], "stored_bytes_per_launch": dom["stored_bytes"],
+                         "frac_stored": dom["frac_stored"], "avg_launch_ms": dom["avg_ms"], "launches": dom["launches"],
+                         "measured_in": ("one-stream repeat of the same %d iterations right after the timed region" % K)
+                         if overlap else "the timed region",
+                         # the same kernel against the other roof it touches: vector instructions per wavefront-stage from
+                         # the SQ counters of the committed one-stream run, priced at the nominal issue rate
+                         "vector_issue": vector_issue(dom, units, T)},
+            "kernels": kernels,
+            "attribution_ms_per_step": float(ms.sum(1).mean())})
+    out.update({
         # whole iteration, per GPU: SURVEY 8d's 496 B per trajectory-stage over the wall time of a step
         "iteration_hbm_frac_per_gpu": ITERATION_BYTES * units * K / el / 1e9 / HBM_PEAK_GBS,
         "per_rank_ms_per_step": [float(every.min() / K * 1e3), float(every.max() / K * 1e3)],
@@ -747,11 +846,10 @@ def run(a):
         "n_nonfinite": int(summ[4].item()),
         "value_finite_only": fin_b * K / el,
         "status_or_rank0": int(np.bitwise_or.reduce(sc["status"])),
-        "provenance": provenance(),
-    }
+        "provenance": provenance()})
     del s, s2, res
     torch.cuda.empty_cache()
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         try:
             it = min(K, 10)
             out["cpu_baseline"], sample, cores = cpu_baseline(pr, x0, it, a.cpu_budget_s)
@@ -760,9 +858,9 @@ def run(a):
         except Exception as e:  # the baseline is a report, never a reason to lose the bench line
             out.setdefault("cpu_baseline", None)
             out["cpu_baseline_error"] = repr(e)
-    else:
+    elif a.full:
         out["cpu_baseline"] = None
-    if not a.no_secondary and Bg >= 65536:
+    if a.full and not a.no_secondary and Bg >= 65536:
         try:
             out["secondary"] = secondary_configs(torch, batch, problems, a.horizon, dev, min(ncand, 3))
         except Exception as e:  # a report beside the headline, never a reason to lose the bench line

@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _bench(tmp, gpus, per_gpu, steps=3, extra=("--cpu-budget-s", "1.5"), light=False, force_choice=False):
+    """bench.py --full (the whole record: every test here checks parts of it beside the headline)"""
     d = tmp / ("n%d_%d" % (gpus, per_gpu))
     d.mkdir()
     env = dict(os.environ, AOC_BENCH_ONE_DEVICE="1", AOC_BENCH_BACKEND="gloo", AOC_BENCH_DUMP=str(d),
@@ -26,7 +27,7 @@ def _bench(tmp, gpus, per_gpu, steps=3, extra=("--cpu-budget-s", "1.5"), light=F
     except Exception:
         pass
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps),
-                        "--warmup", "1", "--batch-per-gpu", str(per_gpu)] + list(extra), env=env,
+                        "--warmup", "1", "--batch-per-gpu", str(per_gpu), "--full"] + list(extra), env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -119,6 +120,7 @@ def test_two_rank_rehearsal_with_placement_candidates_at_the_per_gpu_size(tmp_pa
     assert two["collective"]["world_seen"] == 2 and [int(p["first"]) for p in parts] == [0, 131072]
     assert parts[0]["cost"].shape[0] == 131072 and np.array_equal(parts[0]["summary"], parts[1]["summary"])
     out = os.path.join(ROOT, "gpurun_out", "two_rank_rehearsal_placement.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     json.dump(two, open(out, "w"), indent=1)
 
 

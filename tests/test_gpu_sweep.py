@@ -202,5 +202,5 @@ def test_late_regime_free_running():
            "states_bit_identical": int(strict.sum()), "cost_rel_max_identical_histories": float(cost_rel[same].max()),
            "u_channel_rel_max_strict": float(chan[strict].max()), "parted": int(len(parted)),
            "parted_not_explained_by_teacher_forcing": bad}
-    json.dump(rec, open(os.path.join(ROOT, "gpurun_out", "late_regime_free_running.json"), "w"), indent=1)
+    _dump(rec, "late_regime_free_running.json")
     assert bad <= max(2, len(parted) // 50), rec

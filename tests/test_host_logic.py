@@ -214,7 +214,7 @@ bench.kernel_names = lambda nt, full: {p: p for p in Stub.PASSES}
 bench.provenance = lambda: {}
 a = bench.parse.__globals__["argparse"].Namespace(gpus=int(os.environ["WORLD_SIZE"]), steps=3, warmup=1, batch_per_gpu=int(os.environ["STUB_B"]),
         global_batch=0, cpu_budget_s=1.0, horizon=500, no_cpu_baseline=True, no_secondary=True, no_overlap=os.environ.get("STUB_NO_OVERLAP") == "1",
-        placement_candidates=3)
+        placement_candidates=3, full=os.environ.get("STUB_FULL", "1") == "1", dump_outputs=os.environ.get("STUB_DUMP") or None)
 try:
     bench.run(a)
 finally:
@@ -222,17 +222,12 @@ finally:
 '''
 
 
-@pytest.mark.parametrize("B,no_overlap", [(131072, "0"), (131072, "1"), (4096, "0")])
-def test_every_rank_issues_the_same_sequence_of_collectives(tmp_path, B, no_overlap):
-    """bench.run's control flow on four gloo ranks with the solver stubbed out: every rank must issue the same sequence of
-    collectives whatever its own placement draw (AOC_BENCH_FORCE_CHOICE makes the ranks choose differently), its own free
-    memory (differs by rank here) and its own timings.  Round 4's two deadlocks were rank-dependent branches around
-    collectives (EXPERIMENTS.md); this is the cheap insurance for the driver's SCALE leg."""
+def _stub_run(tmp_path, B, no_overlap, full, port, dump=None):
     script = tmp_path / "stub_worker.py"
     script.write_text(STUB_WORKER % ROOT)
-    port = 29600 + (B // 4096 + int(no_overlap)) % 50
     env = dict(os.environ, OUT=str(tmp_path), MASTER_ADDR="127.0.0.1", AOC_BENCH_BACKEND="gloo", AOC_BENCH_DEVICE="cpu",
-               AOC_BENCH_FORCE_CHOICE="1", STUB_B=str(B), STUB_NO_OVERLAP=no_overlap)
+               AOC_BENCH_FORCE_CHOICE="1", STUB_B=str(B), STUB_NO_OVERLAP=no_overlap, STUB_FULL="1" if full else "0",
+               STUB_DUMP=str(dump or ""))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), str(script)], env=env, timeout=300,
                        capture_output=True, text=True)
@@ -245,3 +240,83 @@ def test_every_rank_issues_the_same_sequence_of_collectives(tmp_path, B, no_over
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 4 and line["collective"]["world_seen"] == 4
     assert line["value"] == pytest.approx(B * 4 * 3 / (line["ms_per_step"] * 3e-3))
+    return line, logs[0]
+
+
+@pytest.mark.parametrize("B,no_overlap", [(131072, "0"), (131072, "1"), (4096, "0")])
+def test_every_rank_issues_the_same_sequence_of_collectives(tmp_path, B, no_overlap):
+    """bench.run's control flow (--full) on four gloo ranks with the solver stubbed out: every rank must issue the same
+    sequence of collectives whatever its own placement draw (AOC_BENCH_FORCE_CHOICE makes the ranks choose differently),
+    its own free memory (differs by rank here) and its own timings.  Round 4's two deadlocks were rank-dependent branches
+    around collectives (EXPERIMENTS.md); this is the cheap insurance for the driver's SCALE leg."""
+    line, _ = _stub_run(tmp_path, B, no_overlap, True, 29600 + (B // 4096 + int(no_overlap)) % 50)
+    assert "kernels" in line and "us" in line["collective"]
+
+
+@pytest.mark.parametrize("B,no_overlap", [(131072, "0"), (131072, "1"), (4096, "0")])
+def test_every_rank_issues_the_same_sequence_of_collectives_in_a_plain_run(tmp_path, B, no_overlap):
+    """The same for a plain run (no --full), which builds only the solver it times and writes --dump-outputs on rank 0:
+    no rank-dependent collective, nothing of --full in the line, the outputs as float64 .npy files."""
+    line, log = _stub_run(tmp_path, B, no_overlap, False, 29660 + (B // 4096 + int(no_overlap)) % 50, dump=tmp_path / "out")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    for key in ("ms_per_step_first_allocated", "steps10", "roofline", "kernels", "cpu_baseline", "secondary"):
+        assert key not in line, key
+    assert "us" not in line["collective"]
+    two = line["config"]["streams"] != "one"
+    assert two == (B >= 131072 and no_overlap == "0")
+    assert ("one_stream_solver" in line["placement_tuning"]) != two      # the one-stream solver only where it is timed
+    dumped = sorted(os.listdir(tmp_path / "out"))
+    assert dumped == sorted(n + ".npy" for n in ("xx_sample", "uu_sample", "sample_index", "scalars_index", "summary",
+                                                 "status", "cost", "finite", "sample_finite"))
+    assert all(np.load(tmp_path / "out" / n).dtype == np.float64 for n in dumped)
+    assert np.array_equal(np.load(tmp_path / "out" / "summary.npy"), [4.0 * B, -8.0 * B, 12.0 * B, 4.0 * B, 0.0])
+
+
+def test_dump_outputs_is_a_seeded_float64_sample_within_64_mb(tmp_path):
+    """bench.dump_outputs: the states and inputs of a fixed sample of trajectories, the per-trajectory scalars of all of
+    them up to DUMP_SCALARS (else of a fixed sample), the summary; float64 and finite (a diverged trajectory is flagged
+    in `finite` / `sample_finite` and written as 0), the same files for the same inputs, 64 MB at most at the default
+    size (131 072 x T = 500, where the scalars of every trajectory are written)."""
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    import torch
+    rng = np.random.default_rng(5)
+
+    def fake(B, T):
+        xx, uu = rng.normal(size=(B, 6, T)), rng.normal(size=(B, 2, T))
+        sc = {"cost": rng.normal(size=B), "ntrials": rng.integers(0, 11, B).astype(np.int32),
+              "status": rng.integers(0, 64, B).astype(np.int32)}
+        bad = rng.choice(B, B // 20, replace=False)            # diverged trajectories: NaN / Inf somewhere in them
+        xx[bad, 1, -1] = np.nan
+        uu[bad[::2], 0, 0] = np.inf
+        sc["cost"][bad[::3]] = np.nan
+        return types.SimpleNamespace(current=lambda: (xx, uu)), sc, xx, uu
+
+    for B, T in ((20000, 50), (300000, 1)):
+        res, sc, xx, uu = fake(B, T)
+        summ = torch.arange(5, dtype=torch.float64)
+        got = []
+        for rep in range(2):
+            d = tmp_path / ("%d_%d_%d" % (B, T, rep))
+            bench.dump_outputs(str(d), res, sc, summ, T)
+            got.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+        a, b = got
+        assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+        assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in a.values())
+        ti, si = a["sample_index"].astype(np.int64), a["scalars_index"].astype(np.int64)
+        assert len(ti) == min(B, bench.DUMP_STAGES // T) and len(si) == min(B, bench.DUMP_SCALARS)
+        assert (np.diff(ti) > 0).all() and (np.diff(si) > 0).all() and ti[-1] < B and si[-1] < B
+        ok_t = np.isfinite(xx[ti]).all((1, 2)) & np.isfinite(uu[ti]).all((1, 2))
+        ok_s = np.isfinite(sc["cost"][si])
+        assert (~ok_t).any() and (~ok_s).any()
+        assert np.array_equal(a["sample_finite"], ok_t) and np.array_equal(a["finite"], ok_s)
+        assert np.array_equal(a["xx_sample"][ok_t], xx[ti][ok_t]) and np.array_equal(a["uu_sample"][ok_t], uu[ti][ok_t])
+        assert not a["xx_sample"][~ok_t].any() and not a["uu_sample"][~ok_t].any()
+        for k in sc:
+            assert np.array_equal(a[k][ok_s], sc[k][si][ok_s]) and not a[k][~ok_s].any(), k
+        assert np.array_equal(a["summary"], np.arange(5.0))
+    # the default size: 1024 trajectories x T = 500 of states and inputs, the scalars of all 131 072 trajectories
+    nbytes = 8 * (1024 * (8 * 500 + 2) + 131072 * (6 + 2) + 5)
+    assert bench.DUMP_STAGES // 500 == 1024 and bench.DUMP_SCALARS >= 131072 and nbytes < 64 * 2 ** 20
