@@ -647,8 +647,9 @@ class GradientBatchSolver(NewtonBatchSolver):
     """B independent GradientMethod.optimize instances (reference optcon.py:27-174): steepest descent,
     du = -(B^T lambda + l_u) from the costate sweep (aoc_gradient), Armijo back-tracking and update through the same
     line search as the Newton iteration (aoc_linesearch with no speculated trials).  The reference's own method cannot
-    run (TypeError at optcon.py:125); this is its loop with the missing JP argument supplied — parity unpinned,
-    checked against the oracle's restatement only.  `descent` holds the slope -sum |du|^2 (the reference prints
+    run (TypeError at optcon.py:125); this is its loop with the missing JP argument supplied, pinned to the reference
+    run that way (G11: cost, direction and, given the reference's slope, every Armijo verdict and new state; DESIGN
+    section 2).  `descent` holds the slope -sum |du|^2 (the reference prints
     +sum |du|^2 and stops when that is <= 1e-6: the same test as slope >= term_cond = -1e-6, so solve() applies
     unchanged, return-index behaviour included)."""
 

@@ -11,7 +11,7 @@ are kept on the object: `.JJ`, `.descent`, `.stepsizes`); `visu_armijo=True` eva
 Armijo figure per iteration (`.armijo_curves`, optcon.py:280-325) and draws it when Matplotlib is importable
 (non-blocking; saved under $AOC_PLOT_DIR if that is set); and
 `GradientMethod.optimize`, which raises TypeError in the reference (8 arguments passed to a
-9-parameter method, optcon.py:125 vs :204), runs here with the missing argument supplied (parity unpinned).
+9-parameter method, optcon.py:125 vs :204), runs here with the missing argument supplied.
 """
 import numpy as np
 
@@ -124,7 +124,12 @@ class GradientMethod:
         raises TypeError (armijo_stepsize is called with 8 of its 9 arguments, :125 vs :204); here the loop runs with the
         missing JP = JJ[kk] supplied and the directional derivative -descent[kk] as the Armijo slope.  Same stdout line
         per iteration, same stopping rule (descent <= 1e-6, the constructor's term_cond ignored, :52) and returned
-        iterate (index kk-1 on convergence, :137-140).  Parity unpinned: checked against the oracle's restatement."""
+        iterate (index kk-1 on convergence, :137-140).  Pinned to the reference's loop run with JP supplied
+        (tests/golden g11_*): the same costs and directions, and with the reference's +descent the same Armijo verdicts.
+        The slope -descent is a second, deliberate repair: with +descent the Armijo test accepts steps that raise the
+        cost.  At the defaults (stepsize_0 = 1e-2) it changes no verdict (0 of 7 iterations on the step manoeuvre,
+        0 of 3 on the acrobatic one).  From stepsize_0 = 10 it changes all of them (7 of 7, 3 of 3): the reference's
+        cost climbs 221.04 -> 4260.97 in 7 iterations, -descent brings it to 128.06."""
         TT = int(tf / dt)                                   # optcon.py:43
         prob = self._problem(TT)
         prm = self._params()

@@ -261,7 +261,7 @@ int aoc_backward(const aoc_problem *prob, int32_t full_hessian, const void *x, c
  * expects (the reference accumulates +sum |du_t|^2 under that name, :123, prints it and stops when it is <= 1e-6).
  * One steepest-descent iteration = aoc_gradient + aoc_linesearch with n_spec = 0 (J_trial = NULL).  The reference's
  * own GradientMethod.optimize cannot run (it calls armijo_stepsize with 8 of its 9 arguments, optcon.py:125 vs :204 —
- * TypeError): this is that loop with the missing JP = JJ[kk] supplied, parity unpinned (oracle restatement only). */
+ * TypeError): this is that loop with the missing JP = JJ[kk] supplied, pinned to the reference run that way (G11). */
 int aoc_gradient(const aoc_problem *prob, const void *x, const double *u, const double *x0, double *du,
                  double *slope, int32_t *status);
 

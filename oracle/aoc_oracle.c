@@ -608,10 +608,10 @@ int orc_newton_optimize(const orc_problem *p, const orc_params *prm, const doubl
 
 /* ------------------------------------------------------------------------------------------
  * One outer iteration of GradientMethod.optimize (optcon.py:86-136), steepest descent.
- * PARITY UNPINNED: the reference's own method raises TypeError at optcon.py:125 (it calls armijo_stepsize with 8 of
- * the 9 arguments of optcon.py:204), so no golden vector exists.  This restates the loop with the one repair that
- * lets it run: JP = JJ[kk] is passed, and the slope handed to armijo_stepsize is the directional derivative
- * -descent[kk] (the reference accumulates descent[kk] = +sum |deltau_t|^2, :123; armijo_stepsize's test
+ * The reference's own method raises TypeError at optcon.py:125 (it calls armijo_stepsize with 8 of the 9 arguments
+ * of optcon.py:204); tests/golden g11_* record it run with JP supplied and nothing else changed.  This restates the
+ * loop with that repair — JP = JJ[kk] is passed — and a second one: the slope handed to armijo_stepsize is the
+ * directional derivative -descent[kk] (the reference accumulates descent[kk] = +sum |deltau_t|^2, :123; armijo_stepsize's test
  * J' > JP + cc*stepsize*descent, :268, needs the negative quantity, as NewtonMethod passes it).
  * out: xx_new, uu_new; JJ, descent (= sum |deltau|^2, what the reference prints), stepsize, ntrials; du (2,T) optional.
  * ------------------------------------------------------------------------------------------ */

@@ -175,6 +175,17 @@ def get_update(prob, stepsize, uu, du, x0):
     return xx_t, uu_t
 
 
+def armijo(prob, prm, uu, du, x0, descent, JP):
+    """armijo_stepsize (optcon.py:204-327): trial ii rolls out u + stepsize_0*beta^ii*du from x0 and is accepted iff
+    J' <= JP + cc*stepsize*descent; `descent` is used as given (its sign is the caller's).  -> (stepsize, ntrials);
+    on exhaustion the untested stepsize_0*beta^armijo_maxiters with ntrials = armijo_maxiters (Q5)."""
+    T = prob.T
+    wx = np.zeros((6, T)); wu = np.zeros((2, T)); ntr = C.c_int()
+    s = lib().orc_armijo(C.byref(prob.c), C.byref(prm), _p(_f64(uu)), _p(_f64(du)), _p(_f64(x0)), C.c_double(descent),
+                         C.c_double(JP), C.byref(ntr), _p(wx), _p(wu))
+    return s, ntr.value
+
+
 def ltv_lqr(AA, BB, QQ, RR, SS, QQf, x0, qq=None, rr=None, qqf=None):
     """Inputs in the reference's layout (.., .., T); outputs in the reference's layout too."""
     T = AA.shape[2]
@@ -211,8 +222,9 @@ def newton_iterate(prob, prm, kk, xx, uu, x0, want_internals=False):
 
 
 def gradient_iterate(prob, prm, xx, uu, x0):
-    """One iteration of GradientMethod.optimize with the missing JP argument supplied (parity unpinned: the
-    reference's method raises TypeError)."""
+    """One iteration of GradientMethod.optimize with the missing JP argument supplied (the reference's method raises
+    TypeError) and the Armijo slope -descent; pinned to the reference run with JP supplied (G11).  Returns descent as
+    the reference prints it, +sum |du|^2."""
     T = prob.T
     xn = np.zeros((6, T)); un = np.zeros((2, T)); du = np.zeros((2, T))
     J = C.c_double(); d = C.c_double(); s = C.c_double(); ntr = C.c_int()

@@ -10,7 +10,17 @@ only.  The driver scripts themselves are NOT imported (they need cvxpy and call
 plt.show/np.save at import); the problem set-up they do is re-stated below from
 main_newton_method.py:32-142 and acrobatic_newton.py:34-154.
 
-Run:  MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python3 tests/golden/make_golden.py [config1]
+Run:  MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python3 tests/golden/make_golden.py [SUBCOMMAND]
+
+Without a subcommand the fixtures g1-g10, problem_* and data_* are written.  A subcommand writes only its own:
+  config1      g8_full_{step,acro}_T1000          the drivers' full solves at T = 1000
+  airfoil      g10_airfoil                        animate.Airfoil outlines and frames
+  gradient     g11_gradient_{step_T500,acro_T1000}  GradientMethod.optimize with the missing JP supplied, every
+                                                  iteration (defaults, and stepsize_0 = 10 to back-track)
+  ltv_general  g12_ltv_general                    the generic ltv_LQR on seeded random problems (dense R, S, affine
+                                                  and broadcast inputs, T = 2 / 3, indefinite and non-symmetric R)
+  step_wide    g13_step_wide                      Dynamics.step at angles over +-4 pi, 1e-9 from every k pi/4, in
+                                                  [2^20, 2^24], and V from 0.05 to 300
 """
 import contextlib
 import io
@@ -294,7 +304,247 @@ def airfoil_vectors():
          point_error=np.array(point_error))
 
 
+class _GradientMethodJP(ref_opt.GradientMethod):
+    """The reference's GradientMethod with the one repair that lets optimize() run: armijo_stepsize is called with 8 of
+    its 9 arguments (optcon.py:125 vs :204); the missing JP is the cost JJ[kk] the caller already passes.  The loop of
+    optcon.py:84-148 and the +sum |du|^2 it hands over as `descent` are the reference's own."""
+
+    def armijo_stepsize(self, uu, deltau, xx_ref, uu_ref, x0, TT, JJ, descent, JP=None):
+        return super().armijo_stepsize(uu, deltau, xx_ref, uu_ref, x0, TT, JJ, descent, JJ)
+
+
+def next_inputs(uu, stepsize, deltau):
+    """The inputs get_update makes (optcon.py:193-196): uu + stepsize*deltau, the last sample 0."""
+    un = uu + stepsize * deltau
+    un[:, -1] = 0.0
+    return un
+
+
+def run_gradient(p, xx_init, uu_init, n_iters, stepsize_0=1e-2, armijo_maxiters=20, cc=0.5, beta=0.7):
+    """GradientMethod(max_iters=n_iters+1).optimize with taps on get_update / armijo_stepsize (as run_newton): per
+    iteration k the iterate k it started from, JJ[k], descent[k] and deltau as handed to Armijo, the accepted step, the
+    trial count and the stdout scalars.  States of iterates k >= 1 are float32 values past sample 0 (stored so)."""
+    cst = ref_air.Cost(p["QQt"], p["RRt"], p["QQT"])
+    GM = _GradientMethodJP(p["dyn"], cst, p["xx_ref"], p["uu_ref"], max_iters=n_iters + 1, stepsize_0=stepsize_0,
+                           cc=cc, beta=beta, armijo_maxiters=armijo_maxiters, visu_armijo=False)
+    iterates, armijo_in, steps, ntrials = [], [], [], []
+    orig_update, orig_armijo = GM.get_update, GM.armijo_stepsize
+    ncalls = {"n": 0}
+    dyn = p["dyn"]
+    orig_step = dyn.step
+
+    def tap_step(*a):
+        ncalls["n"] += 1
+        return orig_step(*a)
+
+    def tap_update(stepsize, uu, deltau, x0):
+        xx_t, uu_t = orig_update(stepsize, uu, deltau, x0)
+        iterates.append((xx_t.copy(), uu_t.copy()))
+        return xx_t, uu_t
+
+    def tap_armijo(uu, deltau, xx_ref, uu_ref, x0, TT, JJ, descent):
+        armijo_in.append((uu.copy(), deltau.copy(), float(JJ), float(descent)))
+        n0 = ncalls["n"]
+        s = orig_armijo(uu, deltau, xx_ref, uu_ref, x0, TT, JJ, descent)
+        ntrials.append((ncalls["n"] - n0) // (p["TT"] - 1))
+        steps.append(float(s))
+        return s
+
+    GM.get_update, GM.armijo_stepsize, dyn.step = tap_update, tap_armijo, tap_step
+    buf = io.StringIO()
+    try:
+        with contextlib.redirect_stdout(buf):
+            GM.optimize(xx_init.copy(), uu_init.copy(), p["tf"], p["dt"])
+    finally:
+        dyn.step = orig_step
+    import matplotlib.pyplot as plt
+    plt.close("all")
+    sc = [(int(a), float(b), float(c)) for a, b, c in ITER_RE.findall(buf.getvalue())]
+    n = len(sc)
+    assert n == n_iters == len(steps) == len(iterates) and [s[0] for s in sc] == list(range(n))
+    J = np.array([a[2] for a in armijo_in]); d = np.array([a[3] for a in armijo_in])
+    assert np.array_equal(J, [s[2] for s in sc]) and np.array_equal(d, [s[1] for s in sc])
+    # what Armijo was handed at iteration k is iterate k; iterate k+1 is what get_update made of it
+    assert np.array_equal(armijo_in[0][0], uu_init)
+    for k in range(1, n):
+        assert np.array_equal(armijo_in[k][0], iterates[k - 1][1])
+    xx_it = np.stack([it[0] for it in iterates])
+    assert np.array_equal(xx_it[:, :, 1:].astype(np.float32), xx_it[:, :, 1:])
+    assert (xx_it[:, :, 0] == xx_init[:, 0]).all()
+    # the inputs of iterate k+1 are not stored: they are uu_k + step_k*deltau_k (last sample 0), bit for bit
+    for k in range(n):
+        assert np.array_equal(iterates[k][1], next_inputs(armijo_in[k][0], steps[k], armijo_in[k][1]))
+    return dict(xx_init=xx_init, uu_init=uu_init, JJ=J, descent=d,
+                deltau=np.stack([a[1] for a in armijo_in]), stepsize=np.array(steps),
+                ntrials=np.array(ntrials, dtype=np.int64), xx_it=xx_it.astype(np.float32),
+                cost_printed=np.array([s[2] for s in sc]),
+                descent_printed=np.array([s[1] for s in sc]), stepsize_0=np.float64(stepsize_0),
+                armijo_maxiters=np.int64(armijo_maxiters), cc=np.float64(cc), beta=np.float64(beta))
+
+
+def gradient_vectors():
+    """G11: GradientMethod.optimize (optcon.py:27-174) with JP supplied, from the reference's own initial guess
+    (the xx_init / uu_init of g6_*): the constructor defaults (stepsize_0 = 1e-2, armijo_maxiters = 20: every step is
+    accepted at its first trial) and stepsize_0 = 10 (back-tracking; the reference's +sum |du|^2 slope then accepts
+    steps that raise the cost).  Keys 'def_*' and 'bt_*'; xx_it[k] holds the states of iterate k+1, whose inputs are
+    next_inputs(inputs of iterate k, stepsize[k], deltau[k])."""
+    for name, p, n_iters in (("g11_gradient_step_T500", step_problem(tf=1.0, dt=2e-3), 7),
+                             ("g11_gradient_acro_T1000", acro_problem(), 3)):
+        xi, ui = p["dyn"].get_initial_trajectory(p["xx_ref"], p["tt"])
+        out = {}
+        for tag, s0 in (("def", 1e-2), ("bt", 10.0)):
+            r = run_gradient(p, xi, ui, n_iters, stepsize_0=s0)
+            if tag == "def":
+                assert (r["ntrials"] == 1).all()
+            else:
+                assert len(set(r["ntrials"].tolist())) >= 3, r["ntrials"]
+            print("  G11 %s %s: steps %s, trials %s, cost %r -> %r" % (name, tag, r["stepsize"].tolist(),
+                  r["ntrials"].tolist(), float(r["JJ"][0]), float(r["JJ"][-1])))
+            for k, v in r.items():
+                if k not in ("xx_init", "uu_init"):
+                    out[tag + "_" + k] = v
+        save(name, xx_init=xi, uu_init=ui, **out)
+
+
+def ltv_general_vectors():
+    """G12: the generic optcon.ltv_LQR (optcon.py:533-771) on seeded random problems the aircraft never produces:
+    dense per-stage A, B, Q, R (SPD, non-diagonal), S != 0, x0 != 0; the same augmented with per-stage qq / rr and a
+    qqf; time-invariant 2-D inputs with 1-D affine terms (the reference repeats them); T = 2 and T = 3; an R_t with a
+    negative eigenvalue at some stages (the gain loop regularises, the Riccati loop does not); a non-symmetric R that
+    gives M complex eigenvalues with positive and negative real parts.  Per case '<case>__<arg>' holds what ltv_LQR was
+    called with ('<case>__base' names the case whose arrays it shares, to keep the file small) and KK, PP, xx, uu and
+    the number of regularised stages (an eigvals tap, as lqr_case)."""
+    rng = np.random.default_rng(20261016)
+
+    def spd(n, lo, hi):
+        Qm, _ = np.linalg.qr(rng.normal(size=(n, n)))
+        return Qm @ np.diag(rng.uniform(lo, hi, n)) @ Qm.T
+
+    def stage_set(T):
+        A = np.stack([0.9 * np.linalg.qr(rng.normal(size=(6, 6)))[0] + 0.08 * rng.normal(size=(6, 6)) for _ in range(T)], -1)
+        return dict(AA=A, BB=0.3 * rng.normal(size=(6, 2, T)), QQ=np.stack([spd(6, 0.1, 2.0) for _ in range(T)], -1),
+                    RR=np.stack([spd(2, 0.05, 1.0) for _ in range(T)], -1), SS=0.05 * rng.normal(size=(2, 6, T)),
+                    QQf=spd(6, 0.5, 5.0), x0=rng.normal(0, 1, 6))
+
+    def affine(T):
+        return dict(qq=rng.normal(0, 1, (6, T)), rr=rng.normal(0, 1, (2, T)), qqf=rng.normal(0, 1, 6))
+
+    T = 40
+    cases = {}
+    for i in (0, 1):
+        cases["plain%d" % i] = stage_set(T)
+        cases["aug%d" % i] = dict(base="plain%d" % i, **affine(T))
+    ti = dict(AA=0.9 * np.linalg.qr(rng.normal(size=(6, 6)))[0] + 0.08 * rng.normal(size=(6, 6)),
+              BB=0.3 * rng.normal(size=(6, 2)), QQ=spd(6, 0.1, 2.0), RR=spd(2, 0.05, 1.0), SS=0.05 * rng.normal(size=(2, 6)),
+              QQf=spd(6, 0.5, 5.0), x0=rng.normal(0, 1, 6))
+    cases["ti_plain"] = dict(TT=T, **ti)
+    cases["ti_aug"] = dict(base="ti_plain", qq=rng.normal(0, 1, 6), rr=rng.normal(0, 1, 2), qqf=rng.normal(0, 1, 6))
+    cases["short2"] = dict(**stage_set(2), **affine(2))
+    cases["short3"] = stage_set(3)
+    # R_t indefinite at every fifth stage: eigenvalues (-1, 0.5) — M = R + B^T P B keeps a negative one
+    Rneg = cases["plain0"]["RR"].copy()
+    for t in range(2, T - 1, 5):
+        Qm, _ = np.linalg.qr(rng.normal(size=(2, 2)))
+        Rneg[:, :, t] = Qm @ np.diag([-1.0, 0.5]) @ Qm.T
+    cases["indef"] = dict(base="plain0", RR=Rneg)
+    cases["indef_aug"] = dict(base="aug0", RR=Rneg)
+    # R = [[a, b], [-b, a]] with |b| >> |B^T P B|: M has a complex pair, real part ~ a (+ / - by stage)
+    Rc = np.zeros((2, 2, T))
+    for t in range(T):
+        a = 0.6 if t % 3 else -2.5
+        Rc[:, :, t] = [[a, 3.0], [-3.0, a]]
+    cases["complex"] = dict(base="plain1", RR=Rc)
+
+    out = {}
+    orig = np.linalg.eigvals
+    for name, c in cases.items():
+        full = dict(c)
+        while "base" in full:
+            b = cases[full.pop("base")]
+            full = {**b, **full}
+        TT = full.get("TT", full["AA"].shape[-1] if full["AA"].ndim == 3 else T)
+        nreg = {"n": 0}
+        cplx = {"pos": 0, "neg": 0}
+
+        def tap(M):
+            w = orig(M)
+            if np.iscomplexobj(w):
+                cplx["pos" if w.real[0] > 0 else "neg"] += 1
+            if not np.all(w > 0):
+                nreg["n"] += 1
+            return w
+
+        buf = io.StringIO()
+        np.linalg.eigvals = tap
+        try:
+            with contextlib.redirect_stdout(buf):
+                KK, PP, xx, uu = ref_opt.ltv_LQR(full["AA"], full["BB"], full["QQ"], full["RR"], full["SS"], full["QQf"],
+                                                 TT, full["x0"], full.get("qq"), full.get("rr"), full.get("qqf"))
+        finally:
+            np.linalg.eigvals = orig
+        aug = any(k in full for k in ("qq", "rr", "qqf"))
+        assert buf.getvalue() == ("Augmented term!\n" if aug else "")
+        assert np.isfinite(KK).all() and np.isfinite(PP).all() and np.isfinite(xx).all()
+        for k, v in c.items():
+            out["%s__%s" % (name, k)] = np.array(v) if k == "base" else v
+        out["%s__TT" % name] = np.int64(TT)
+        out.update({"%s__KK" % name: KK, "%s__PP" % name: PP, "%s__xx" % name: xx.copy(), "%s__uu" % name: uu.copy(),
+                    "%s__n_regularised" % name: np.int64(nreg["n"])})
+        print("  G12 %-10s T=%-3d aug=%d regularised stages %d, complex M (Re>0 / Re<0) %d / %d, max|KK| %.3g max|PP| %.3g"
+              % (name, TT, aug, nreg["n"], cplx["pos"], cplx["neg"], np.abs(KK).max(), np.abs(PP).max()))
+        if name.startswith("indef"):
+            assert nreg["n"] > 0
+        if name == "complex":
+            assert cplx["pos"] > 0 and cplx["neg"] > 0 and nreg["n"] >= cplx["neg"]
+    save("g12_ltv_general", cases=np.array(list(cases)), **out)
+
+
+def step_wide_vectors():
+    """G13: Dynamics.step (aircraft_simplified.py:263-393) with lmbd beyond G1's box: theta, gamma and theta-gamma over
+    +-4 pi, at points within 1e-9 of every k pi/4 on both sides (where a quadrant of the argument reduction changes), a
+    few angles in [2^20, 2^24] and their negatives, V from 0.05 to 300 (log-uniform); inputs and costates as G1."""
+    rng = np.random.default_rng(20261017)
+    dyn = ref_air.Dynamics()
+    dyn.dt = 1e-3
+    ks = np.arange(-16, 17) * (np.pi / 4)
+    near = np.concatenate([ks - rng.uniform(1e-11, 1e-9, ks.size), ks + rng.uniform(1e-11, 1e-9, ks.size)])
+    m = near.size
+    wide = lambda n: rng.uniform(-4 * np.pi, 4 * np.pi, n)
+    th = np.concatenate([near, wide(m), np.zeros(m)])
+    ga = np.concatenate([wide(m), near, np.zeros(m)])
+    th[2 * m:] = wide(m)
+    ga[2 * m:] = th[2 * m:] - near                         # theta - gamma near k pi/4
+    huge = rng.uniform(2.0 ** 20, 2.0 ** 24, 3)
+    huge = np.concatenate([huge, -huge])
+    th = np.concatenate([th, huge, rng.uniform(-3, 3, 6), huge[::-1]])
+    ga = np.concatenate([ga, rng.uniform(-3, 3, 6), huge, huge])
+    n = th.size
+    X = np.stack([rng.uniform(-5, 20, n), rng.uniform(-3, 5, n), np.exp(rng.uniform(np.log(0.05), np.log(300), n)),
+                  th, rng.uniform(-25, 25, n), ga], 1)
+    X[:4, 2] = (0.05, 300.0, 0.05, 300.0)
+    U = np.stack([rng.uniform(0, 900, n), rng.uniform(-100, 300, n)], 1)
+    L = rng.normal(0, 50, (n, 6))
+    xp = np.zeros((n, 6), np.float32); fx = np.zeros((n, 6, 6)); fu = np.zeros((n, 2, 6))
+    fxx = np.zeros((n, 6, 6)); fuu = np.zeros((n, 2, 2)); fux = np.zeros((n, 2, 6))
+    fxx3 = np.zeros((n, 6, 6, 6)); fux3 = np.zeros((n, 2, 6, 6)); fuu3 = np.zeros((n, 2, 2, 6))
+    for i in range(n):
+        xp[i], fx[i], fu[i], fxx[i], fuu[i], fux[i] = dyn.step(X[i], U[i], L[i])
+        r = dyn.step(X[i], U[i])
+        assert np.array_equal(r[0], xp[i])
+        fxx3[i], fuu3[i], fux3[i] = r[3], r[4], r[5]
+    assert np.isfinite(fx).all() and np.isfinite(fxx).all() and np.isfinite(xp).all()
+    sel = np.r_[0:4, m - 2:m + 2, 3 * m:3 * m + 4]        # uncontracted tensors: extreme V, both sides of 0, huge angles
+    save("g13_step_wide", x=X, u=U, lmbd=L, dt=np.float64(dyn.dt), xp=xp, fx=fx, fu=fu, fxx=fxx, fuu=fuu, fux=fux,
+         sel3=sel, fxx3=fxx3[sel], fuu3=fuu3[sel], fux3=fux3[sel])
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "gradient":
+        return gradient_vectors()
+    if len(sys.argv) > 1 and sys.argv[1] == "ltv_general":
+        return ltv_general_vectors()
+    if len(sys.argv) > 1 and sys.argv[1] == "step_wide":
+        return step_wide_vectors()
     if len(sys.argv) > 1 and sys.argv[1] == "airfoil":     # only the fixture added in round 5
         return airfoil_vectors()
     if len(sys.argv) > 1 and sys.argv[1] == "config1":   # only the fixtures added in round 2

@@ -189,3 +189,31 @@ def test_newton_method_like_main_script(mods):
         ns, ni = 3, 1
     with pytest.raises(TypeError):
         optcon.NewtonMethod(Other(), cst, pg["xx_ref"], pg["uu_ref"]).optimize(f["xx_init"], f["uu_init"], 1.0, 2e-3)
+
+
+@pytest.mark.parametrize("case", ["ti_plain", "ti_aug", "short2", "complex"])
+def test_ltv_lqr_broadcasting_vs_reference(mods, case):
+    """optcon.ltv_LQR called as the reference was called for G12 (make_golden.py ltv_general): time-invariant 2-D
+    matrices with 1-D qq / rr / qqf (the reference repeats them over T), T = 2, a non-symmetric R.  The 'Augmented term!'
+    line exactly when an affine term is given; KK, PP, xx, uu within 1e-10 of each entry's scale over t (1e-8 where the
+    gain loop regularises)."""
+    _, optcon, _ = mods
+    g = load_golden("g12_ltv_general")
+    T = int(g[case + "__TT"])
+    a, c = {}, case
+    while c is not None:
+        for k in ("AA", "BB", "QQ", "RR", "SS", "QQf", "x0", "qq", "rr", "qqf"):
+            if k not in a and "%s__%s" % (c, k) in g:
+                a[k] = g["%s__%s" % (c, k)]
+        c = str(g["%s__base" % c]) if "%s__base" % c in g else None
+    aug = "qq" in a
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        KK, PP, xx, uu = optcon.ltv_LQR(a["AA"], a["BB"], a["QQ"], a["RR"], a["SS"], a["QQf"], T, a["x0"],
+                                        a.get("qq"), a.get("rr"), a.get("qqf"))
+    assert buf.getvalue() == ("Augmented term!\n" if aug else "")
+    tol = 1e-8 if int(g[case + "__n_regularised"]) else 1e-10
+    for got, key in ((KK, "KK"), (PP, "PP"), (xx, "xx"), (uu, "uu")):
+        ref = g["%s__%s" % (case, key)]
+        assert got.shape == ref.shape, key
+        assert scaled_err(got, ref) < tol, (key, scaled_err(got, ref))

@@ -6,6 +6,9 @@ the reference's float32 state rounding bit-exact.  The float32 rounding makes wh
 comparison discontinuous: a last-bit difference in u can flip one rounding and move every later
 state by an fp32 ulp.  Chains are therefore checked both free-running and "teacher-forced" (every
 iteration restarted from the golden iterate), and flips — if any — are counted, not hidden."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -985,3 +988,90 @@ def test_four_wavefront_backward_equals_the_others(aoc, tuned):
             assert np.array_equal(outs[0][1][0], xx) and np.array_equal(outs[0][1][1], uu), case
             for key in ("KK", "du", "descent", "lmbd0", "J_trial0", "status"):
                 assert np.array_equal(outs[0][2][key], o[key]), (case, key)
+
+
+# ----------------------------------------------------------------------------------------------
+# G12 / G13 (make_golden.py ltv_general | step_wide): generic ltv_LQR and Dynamics.step beyond the aircraft's range
+# ----------------------------------------------------------------------------------------------
+G12_CASES = ["plain0", "aug0", "plain1", "aug1", "ti_plain", "ti_aug", "short2", "short3", "indef", "indef_aug", "complex"]
+
+
+def _record(name, rec):
+    """Measured errors of a test (DESIGN section 2 quotes them), written as JSON into the directory that
+    AOC_TEST_RECORDS names; nothing is written when it is unset."""
+    d = os.environ.get("AOC_TEST_RECORDS")
+    if d:
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, name), "w") as f:
+            json.dump(rec, f, indent=1)
+
+
+def g12_args(g, case):
+    """ltv_LQR's arguments for one G12 case, broadcast over T as the reference does (optcon.py:552-651): shared arrays
+    come from the case named by '<case>__base'; 2-D matrices and 1-D affine terms repeated over T."""
+    T = int(g[case + "__TT"])
+    a, c = {}, case
+    while c is not None:
+        for k in ("AA", "BB", "QQ", "RR", "SS", "QQf", "x0", "qq", "rr", "qqf"):
+            if k not in a and "%s__%s" % (c, k) in g:
+                a[k] = g["%s__%s" % (c, k)]
+        c = str(g["%s__base" % c]) if "%s__base" % c in g else None
+    for k in ("AA", "BB", "QQ", "RR", "SS"):
+        if a[k].ndim == 2:
+            a[k] = np.repeat(a[k][:, :, None], T, axis=2)
+    for k in ("qq", "rr"):
+        if k in a and a[k].ndim == 1:
+            a[k] = np.repeat(a[k][:, None], T, axis=1)
+    return a, T
+
+
+@pytest.mark.parametrize("case", G12_CASES)
+def test_ltv_lqr_batch_general_vs_reference(aoc, case):
+    """aoc_ltv_lqr (k_ltv_lqr<6> / <7>) on the G12 problems, each replicated to 65 lanes (a full and a ragged
+    workgroup): the copies bit-identical, KK, PP, xx, uu within 1e-10 of each entry's scale over t of the reference's
+    (1e-8 where the gain loop regularises: M + 0.5 I can be nearly singular there, max |KK| 133), and the reference's
+    count of regularised stages — which the kernel decides by a closed-form trace / determinant / discriminant test
+    instead of np.all(eigvals(M) > 0), complex spectra of a non-symmetric R included."""
+    g = load_golden("g12_ltv_general")
+    a, T = g12_args(g, case)
+    nb = 65
+    tm = lambda v: np.repeat(np.ascontiguousarray(np.moveaxis(v, -1, 0))[None], nb, 0)
+    rep = lambda v: None if v is None else np.repeat(np.asarray(v)[None], nb, 0)
+    KK, PP, xx, uu, nreg, nsing = aoc.ltv_lqr_batch(tm(a["AA"]), tm(a["BB"]), tm(a["QQ"]), tm(a["RR"]), tm(a["SS"]),
+                                                    rep(a["QQf"]), rep(a["x0"]), None if "qq" not in a else tm(a["qq"]),
+                                                    None if "rr" not in a else tm(a["rr"]), rep(a.get("qqf")))
+    for v in (KK, PP, xx, uu, nreg, nsing):
+        assert all(np.array_equal(v[0], v[b]) for b in range(1, nb))
+    assert (nsing == 0).all()
+    n_ref = int(g[case + "__n_regularised"])
+    assert nreg[0] == n_ref
+    tol = 1e-8 if n_ref else 1e-10
+    errs = {}
+    for got, key in ((np.moveaxis(KK[0], 0, -1), "KK"), (np.moveaxis(PP[0], 0, -1), "PP"), (xx[0].T, "xx"), (uu[0].T, "uu")):
+        ref = g["%s__%s" % (case, key)]
+        assert got.shape == ref.shape, key
+        errs[key] = scaled_err(got, ref)
+        assert errs[key] < tol, (key, errs[key])
+    _record("g12_%s.json" % case, dict(case=case, T=T, lanes=nb, n_regularised=n_ref, tol=tol, scaled_err=errs))
+
+
+def test_step_batch_wide_angles_vs_golden(aoc):
+    """aoc_step_batch on G13: theta, gamma, theta-gamma over +-4 pi with points 1e-9 either side of every k pi/4 (each
+    quadrant of sincos_fast's reduction, both sides of its boundaries), angles in [2^20, 2^24] (the library fallback)
+    and V from 0.05 to 300 (rcp_fast).  Gates of test_step_batch_vs_golden.  Measured: fx 3.9e-13 relative, all of it at
+    one entry.  At point 133 (V = 49.3, theta - gamma = -15 pi/4 - 5e-10) fx[2, 2] = 1 - (dt/m) dD/dV = -4.6e-4: the
+    two terms cancel 2150-fold.  The device forms the product in another association and fuses the subtraction
+    (linearise_va, contraction on); its result is 1.8e-16 off, 0.8 of a unit in the last place of the terms.  Every
+    other entry is within 3e-15 (fu 4e-16, fxx and fux 7e-16 of their scale)."""
+    g = load_golden("g13_step_wide")
+    xp, fx, fu, fxx, fuu, fux = aoc.step_batch(aoc.default_model(float(g["dt"])), g["x"], g["u"], g["lmbd"])
+    errs = dict(xp_f32_mismatches=int((xp.astype(np.float32) != g["xp"]).sum()), fx=rel_err(fx, g["fx"], 1e-12),
+                fu=rel_err(fu, g["fu"], 1e-12), fxx=scaled_err(fxx.reshape(-1, 36), g["fxx"].reshape(-1, 36)),
+                fux=scaled_err(fux.reshape(-1, 12), g["fux"].reshape(-1, 12)))
+    _record("g13_step_wide.json", dict(points=int(g["x"].shape[0]), errors=errs))
+    assert np.array_equal(xp.astype(np.float32), g["xp"])
+    assert errs["fx"] < 1e-12
+    assert errs["fu"] < 1e-12
+    assert errs["fxx"] < 1e-12
+    assert errs["fux"] < 1e-12
+    assert not fuu.any()

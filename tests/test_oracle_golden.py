@@ -179,9 +179,9 @@ def test_g9_minibatch():
 
 
 def test_gradient_method_restatement_descends():
-    """GradientMethod.optimize (optcon.py:27-174) restated with the missing JP argument: PARITY UNPINNED (the
-    reference's method raises TypeError, optcon.py:125 vs :204; no golden vector can exist).  Sanity only: the
-    direction is the negative gradient, every accepted step satisfies the Armijo inequality, the cost decreases."""
+    """GradientMethod.optimize (optcon.py:27-174) restated with the missing JP argument and the slope -sum |du|^2:
+    the properties of a descent method (the direction is the negative gradient, every accepted step satisfies the
+    Armijo inequality, the cost decreases).  Parity with the reference: test_g11_gradient_method_teacher_forced."""
     g, p = _prob("problem_step_T500")
     c = load_golden("g6_chain_step_T500")
     prm = orc.params(stepsize_0=1e-1, armijo_maxiters=20)
@@ -198,3 +198,127 @@ def test_gradient_method_restatement_descends():
         J.append(r["J"])
         xx, uu = r["xx"], r["uu"]
     assert abs(J[0] - c["cost"][0]) <= 1e-12 * J[0] and all(b < a for a, b in zip(J, J[1:]))
+
+
+# ----------------------------------------------------------------------------------------------
+# G11-G13 (make_golden.py gradient | ltv_general | step_wide): the surfaces the Newton chains do not reach
+# ----------------------------------------------------------------------------------------------
+G11 = [("g11_gradient_step_T500", "problem_step_T500"), ("g11_gradient_acro_T1000", "problem_acro_T1000")]
+
+
+def g11_iterates(g, run):
+    """(xx_k, uu_k) for every iteration k the reference ran: k = 0 is its initial guess; the states of k >= 1 are stored
+    as float32 (sample 0 is x0), their inputs are uu_{k-1} + step*deltau_{k-1} with the last sample 0 (get_update,
+    optcon.py:193-196; the generator asserts this bit for bit)."""
+    xx, uu = [g["xx_init"]], [g["uu_init"]]
+    for k in range(len(g[run + "_JJ"]) - 1):
+        x = g[run + "_xx_it"][k].astype(np.float64)
+        x[:, 0] = g["xx_init"][:, 0]
+        u = uu[-1] + g[run + "_stepsize"][k] * g[run + "_deltau"][k]
+        u[:, -1] = 0.0
+        xx.append(x); uu.append(u)
+    return xx, uu
+
+
+@pytest.mark.parametrize("run", ["def", "bt"])
+@pytest.mark.parametrize("name,prob", G11)
+def test_g11_gradient_method_teacher_forced(name, prob, run):
+    """GradientMethod.optimize of the reference, repaired only by passing JP = JJ[kk] (make_golden.py gradient), pinned
+    iteration by iteration: the oracle's costate sweep from each recorded iterate gives the reference's J, deltau and
+    +sum |deltau|^2; the reference's own Armijo rule (positive descent, JP = J) on the recorded deltau accepts the same
+    step after the same number of trials; get_update with that step gives the next recorded iterate (float32 states
+    bit for bit).  'def': constructor defaults (stepsize_0 = 1e-2, every step accepted at once); 'bt': stepsize_0 = 10,
+    back-tracking with several trial counts."""
+    _, p = _prob(prob)
+    g = load_golden(name)
+    prm = orc.params(stepsize_0=float(g[run + "_stepsize_0"]), armijo_maxiters=int(g[run + "_armijo_maxiters"]),
+                     cc=float(g[run + "_cc"]), beta=float(g[run + "_beta"]))
+    xs, us = g11_iterates(g, run)
+    x0 = g["xx_init"][:, 0]
+    n = len(g[run + "_JJ"])
+    assert len(set(g[run + "_ntrials"].tolist())) >= (1 if run == "def" else 3)
+    for k in range(n):
+        J, dref, d = g[run + "_JJ"][k], g[run + "_deltau"][k], g[run + "_descent"][k]
+        assert J == g[run + "_cost_printed"][k] and d == g[run + "_descent_printed"][k]
+        r = orc.gradient_iterate(p, prm, xs[k], us[k], x0)
+        assert abs(r["J"] - J) <= 1e-12 * abs(J), k
+        assert scaled_err(r["du"], dref) < 1e-10, k
+        assert abs(r["descent"] - d) <= 1e-10 * d, k
+        s, ntr = orc.armijo(p, prm, us[k], dref, x0, d, J)
+        assert (s, ntr) == (g[run + "_stepsize"][k], g[run + "_ntrials"][k]), k
+        xn, un = orc.get_update(p, s, us[k], dref, x0)
+        assert np.array_equal(xn[:, 1:], g[run + "_xx_it"][k][:, 1:].astype(np.float64)), k
+        if k + 1 < n:
+            assert rel_err(un, us[k + 1], 1e-3) < 1e-10, k
+            assert abs(orc.traj_cost(p, xn, un) - g[run + "_JJ"][k + 1]) <= 1e-12 * g[run + "_JJ"][k + 1], k
+
+
+def g12_case(g, case):
+    """The arguments ltv_LQR was called with for one G12 case: '<case>__<arg>', else those of the case named by
+    '<case>__base' (recursively) — in the reference's layout, 2-D / 1-D inputs as given (not broadcast)."""
+    names = ("AA", "BB", "QQ", "RR", "SS", "QQf", "x0", "qq", "rr", "qqf")
+    a, c = {}, case
+    while True:
+        for k in names:
+            if k not in a and "%s__%s" % (c, k) in g:
+                a[k] = g["%s__%s" % (c, k)]
+        if "%s__base" % c not in g:
+            return a
+        c = str(g["%s__base" % c])
+
+
+def g12_broadcast(a, T):
+    """ltv_LQR's own broadcasting (optcon.py:552-651): 2-D matrices repeated over T, 1-D affine terms too."""
+    b = dict(a)
+    for k in ("AA", "BB", "QQ", "RR", "SS"):
+        if b[k].ndim == 2:
+            b[k] = np.repeat(b[k][:, :, None], T, axis=2)
+    for k in ("qq", "rr"):
+        if k in b and b[k].ndim == 1:
+            b[k] = np.repeat(b[k][:, None], T, axis=1)
+    return b
+
+
+G12_CASES = ["plain0", "aug0", "plain1", "aug1", "ti_plain", "ti_aug", "short2", "short3", "indef", "indef_aug", "complex"]
+
+
+def test_g12_case_list():
+    assert [str(c) for c in load_golden("g12_ltv_general")["cases"]] == G12_CASES
+
+
+@pytest.mark.parametrize("case", G12_CASES)
+def test_g12_ltv_lqr_general(case):
+    """optcon.ltv_LQR on problems the aircraft never produces (make_golden.py ltv_general): dense R, S != 0, x0 != 0,
+    affine terms, broadcast 2-D / 1-D inputs, T = 2 and 3, indefinite and non-symmetric R.  KK, PP, xx, uu within 1e-10
+    of each entry's scale over t (1e-8 where the gain loop regularises) and the same number of regularised stages."""
+    g = load_golden("g12_ltv_general")
+    T = int(g[case + "__TT"])
+    a = g12_broadcast(g12_case(g, case), T)
+    KK, PP, xx, uu, nreg, ns = orc.ltv_lqr(a["AA"], a["BB"], a["QQ"], a["RR"], a["SS"], a["QQf"], a["x0"],
+                                           a.get("qq"), a.get("rr"), a.get("qqf"))
+    assert ns == 0
+    assert nreg == int(g[case + "__n_regularised"])
+    tol = 1e-8 if nreg else 1e-10
+    for got, key in ((KK, "KK"), (PP, "PP"), (xx, "xx"), (uu, "uu")):
+        ref = g["%s__%s" % (case, key)]
+        assert got.shape == ref.shape, key
+        assert scaled_err(got, ref) < tol, (key, scaled_err(got, ref))
+
+
+def test_g13_step_wide():
+    """Dynamics.step beyond G1's box (make_golden.py step_wide): angles over +-4 pi with points 1e-9 either side of
+    every k pi/4, angles in [2^20, 2^24], V from 0.05 to 300.  Gates of test_g1_step."""
+    g = load_golden("g13_step_wide")
+    mdl = orc.default_model(float(g["dt"]))
+    for i in range(g["x"].shape[0]):
+        xp, fx, fu, fxx, fuu, fux = orc.step(mdl, g["x"][i], g["u"][i], g["lmbd"][i])
+        assert np.array_equal(xp.astype(np.float32), g["xp"][i]), i
+        assert rel_err(fx, g["fx"][i], 1e-12) < 1e-12, i
+        assert rel_err(fu, g["fu"][i], 1e-12) < 1e-12, i
+        assert rel_err(fxx, g["fxx"][i], 1e-9) < 1e-12, i
+        assert rel_err(fux, g["fux"][i], 1e-9) < 1e-12, i
+        assert not fuu.any() and not g["fuu"][i].any()
+    for j, i in enumerate(g["sel3"]):
+        r = orc.step(mdl, g["x"][i], g["u"][i], None, want3=True)
+        assert rel_err(r[3], g["fxx3"][j], 1e-12) < 1e-12
+        assert rel_err(r[5], g["fux3"][j], 1e-12) < 1e-12
