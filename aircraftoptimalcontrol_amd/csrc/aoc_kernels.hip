@@ -212,6 +212,21 @@ static int check_problem(const aoc_problem* p) {
     return AOC_OK;
 }
 
+// Q and Q_T must be symmetric where the Riccati recursion runs: its kernels carry P as a symmetric matrix and read only
+// the upper triangle of Q and Q_T, while the cost gradients use the full matrices.  Exact comparison, as for R.  The
+// entry points that evaluate costs, rollouts and gradients only (and the generic aoc_ltv_lqr) accept any Q.
+static int check_riccati_weights(const aoc_problem* p, const char* who) {
+    const struct { const double* M; const char* name; } w[2] = {{p->QQt, "QQt"}, {p->QQT, "QQT"}};
+    for (const auto& m : w)
+        for (int i = 0; i < 6; i++)
+            for (int j = i + 1; j < 6; j++)
+                if (m.M[i * 6 + j] != m.M[j * 6 + i])
+                    return einval("%s: aoc_problem.%s is not symmetric (%s[%d][%d] = %.17g, %s[%d][%d] = %.17g): the Riccati "
+                                  "recursion needs Q = Q^T and Q_T = Q_T^T", who, m.name, m.name, i, j, m.M[i * 6 + j], m.name,
+                                  j, i, m.M[j * 6 + i]);
+    return AOC_OK;
+}
+
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Diagnostic timeline of aoc_newton_solve (aoc_solve_trace, include/aoc.h): one row per iteration launched.

@@ -118,6 +118,7 @@ static void hcut_launch_chain(int ntiles, int S, real* scratch, hipStream_t st) 
 static int api_backward(const aoc_problem* p, int32_t full_hessian, const void* x, const real* u, const real* x0,
                  real* Kt, real* lmbd0, int32_t* status, void* scratch = nullptr, size_t scratch_bytes = 0, int hcut_ntiles = 0) {
     int rc = check_problem(p);
+    if (!rc) rc = check_riccati_weights(p, "aoc_backward");
     if (rc) return rc;
     if (!x || !u || !x0 || !Kt) return AOC_EINVAL;
     KConst k = make_const(p);
@@ -477,6 +478,7 @@ static int api_lqr_tracking(const aoc_problem* p, const void* x_opt, const real*
                      const real* x0_reg, real* Kgain, void* x_reg, real* u_reg, int32_t* status,
                      void* scratch = nullptr, size_t scratch_bytes = 0) {
     int rc = check_problem(p);
+    if (!rc) rc = check_riccati_weights(p, "aoc_lqr_tracking");
     if (rc) return rc;
     if (!x_opt || !u_opt || !x_opt0 || !Kgain) return AOC_EINVAL;
     if ((x_reg == nullptr) != (u_reg == nullptr) || (x_reg && !x0_reg)) return AOC_EINVAL;
@@ -595,6 +597,7 @@ static int api_newton_iterate(const aoc_problem* p, const aoc_params* prm, int32
                        real* J_new, real* descent, real* stepsize, int32_t* ntrials, int32_t* status,
                        LsFrozen frozen = LsFrozen{nullptr, nullptr}, int hcut_ntiles = 0) {
     int rc = check_problem(p);
+    if (!rc) rc = check_riccati_weights(p, sizeof(real) == 8 ? "aoc_newton_iterate" : "aoc_newton_iterate_f32");
     if (rc) return rc;
     if (!prm || !workspace) return einval("aoc_newton_iterate: NULL argument");
     if (workspace_bytes < ws_base_bytes(p->B, p->T))

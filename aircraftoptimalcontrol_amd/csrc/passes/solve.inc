@@ -540,6 +540,7 @@ static int api_newton_solve(const aoc_problem* p, const aoc_params* prm, const v
                             int32_t* iters, int32_t* ret_index, int32_t* status, real* h_cost, real* h_desc,
                             real* h_step, int32_t* h_ntr, int32_t* n_run, void* stream2) {
     int rc = check_problem(p);
+    if (!rc) rc = check_riccati_weights(p, stream2 ? "aoc_newton_solve2" : "aoc_newton_solve");
     if (rc) return rc;
     if (!prm || !x_init || !u_init || !x0 || !workspace || !x_star || !u_star || !iters || !ret_index || !status)
         return AOC_EINVAL;
@@ -657,8 +658,10 @@ static int api_mpc_step(const aoc_problem* p_track, const aoc_problem* p_next, c
                         real* descent, real* stepsize, int32_t* ntrials, int32_t* status, real* K0, real* u_applied,
                         int32_t* final_slot, const aoc_mpc_noise* noise = nullptr, real* disturbance_out = nullptr) {
     int rc = check_problem(p_track);
+    if (!rc) rc = check_riccati_weights(p_track, "aoc_mpc_step (p_track)");
     if (rc) return rc;
     rc = check_problem(p_next);
+    if (!rc) rc = check_riccati_weights(p_next, "aoc_mpc_step (p_next)");
     if (rc) return rc;
     if (p_track->B != p_next->B || p_track->T != p_next->T || p_next->T < 3) return AOC_EINVAL;
     if (!prm || n_newton < 0 || !x_cur || !u_cur || !x0 || !x_true || !workspace || !Kgain || !x_a || !u_a || !x_b || !u_b ||

@@ -90,9 +90,11 @@ typedef struct aoc_model {
  * curves (NewtonMethod.__init__ xx_ref/uu_ref, optcon.py:335-339) + batch geometry. */
 typedef struct aoc_problem {
     aoc_model model;
-    double QQt[36];   /* row-major 6x6 */
-    double RRt[4];    /* row-major 2x2 */
-    double QQT[36];   /* row-major 6x6 */
+    double QQt[36];   /* row-major 6x6; exactly symmetric for the entry points that run the Riccati recursion
+                         (aoc_backward, aoc_newton_iterate(_f32), aoc_newton_solve(2), aoc_lqr_tracking, aoc_mpc_step:
+                         AOC_EINVAL otherwise); any matrix for the cost, rollout, gradient, forward and line-search ones */
+    double RRt[4];    /* row-major 2x2, exactly symmetric (every entry point) */
+    double QQT[36];   /* row-major 6x6; the same rule as QQt */
     int32_t B;        /* trajectories */
     int32_t T;        /* samples per trajectory = int(tf/dt), optcon.py:378 (T-1 stages) */
     int32_t x_in_f32; /* element type of the tiled STATE arrays a call reads: 0 = fp64, 1 = float32 */

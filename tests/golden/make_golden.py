@@ -21,6 +21,9 @@ Without a subcommand the fixtures g1-g10, problem_* and data_* are written.  A s
                                                   and broadcast inputs, T = 2 / 3, indefinite and non-symmetric R)
   step_wide    g13_step_wide                      Dynamics.step at angles over +-4 pi, 1e-9 from every k pi/4, in
                                                   [2^20, 2^24], and V from 0.05 to 300
+  dense        g14_dense_step_T500, g14_dense_nonsym_q_step_T500, g14_ltv_nonsym
+                                                  NewtonMethod with dense symmetric weights and with a non-symmetric Q
+                                                  (11 iterations, every iterate), ltv_LQR with non-symmetric Q and Qf
 """
 import contextlib
 import io
@@ -538,7 +541,91 @@ def step_wide_vectors():
          sel3=sel, fxx3=fxx3[sel], fuu3=fuu3[sel], fux3=fux3[sel])
 
 
+def sym_upper(M):
+    """The symmetric matrix of M's upper triangle, exactly (not left to whether NumPy computes A @ A.T with syrk)."""
+    return np.triu(M) + np.triu(M, 1).T
+
+
+def dense_weights(p, seed=0):
+    """The dense weights of tests/test_gpu_edges.py::_setup(dense=True): Q += A A^T (A ~ 1e-3 N(0, 1)), Q_T += A A^T
+    (1e-2), R01 = R10 = 2e-7, each made exactly symmetric."""
+    rng = np.random.default_rng(seed)
+    Q, R, QT = p["QQt"].copy(), p["RRt"].copy(), p["QQT"].copy()
+    for M, sc in ((Q, 1e-3), (QT, 1e-2)):
+        A = rng.normal(size=(6, 6)) * sc
+        M += A @ A.T
+    R += np.array([[0.0, 2e-7], [2e-7, 0.0]])
+    return sym_upper(Q), sym_upper(R), sym_upper(QT)
+
+
+def dense_vectors():
+    """G14: dense weights.  (a) dense symmetric Q, R, Q_T on the step problem at T = 500: NewtonMethod from the
+    reference's own initial guess, 11 iterations (the Hessian switch at kk = 9 crossed), every iterate kept.  (b) the same
+    with Q made non-symmetric by upper-triangle noise of 1e-3 of the diagonal scale (Q_T symmetric): the
+    reference uses the full matrix (aircraft_simplified.py:61-68).  (c) the generic ltv_LQR (optcon.py:533-771) on one
+    seeded problem whose per-stage Q and whose Qf are not symmetric, with affine terms."""
+    p5 = step_problem(tf=1.0, dt=2e-3)
+    xi, ui = p5["dyn"].get_initial_trajectory(p5["xx_ref"], p5["tt"])
+    Q, R, QT = dense_weights(p5)
+    # the scale of the noise: the mean diagonal entry of the dense part added to the driver's Q (~6e-6).  Scaled by
+    # sqrt(Q_ii Q_jj) instead, the reference itself meets a NaN in eigvals within 11 iterations: the antisymmetric part
+    # of P grows without bound through the Riccati recursion (|P| ~ 7e11 at kk = 0).  Even this noise moves the step by
+    # O(1) of the input channels if Q is mirrored from its upper triangle.
+    rng = np.random.default_rng(20261018)
+    Qn = Q + np.triu(rng.normal(size=(6, 6)), 1) * 1e-3 * (Q - p5["QQt"]).diagonal().mean()
+    assert not np.array_equal(Qn, Qn.T) and np.array_equal(Q, Q.T) and np.array_equal(QT, QT.T)
+    n_it = 11
+    for name, Qc in (("g14_dense_step_T500", Q), ("g14_dense_nonsym_q_step_T500", Qn)):
+        p = dict(p5, QQt=Qc, RRt=R, QQT=QT)
+        r, _ = run_newton(p, xi, ui, n_it, range(1, n_it + 1))
+        assert int(r["n_done"]) == n_it, int(r["n_done"])
+        save(name, QQt=Qc, RRt=R, QQT=QT, **r)
+        print("  G14 %s: steps %s, trials %s, cost %r -> %r" % (name, r["stepsize"].tolist(), r["ntrials"].tolist(),
+                                                               float(r["cost"][0]), float(r["cost"][-1])))
+    # (c) generic ltv_LQR, T = 40: SPD-plus-noise Q_t (non-symmetric at every stage), non-symmetric Qf
+    rng = np.random.default_rng(20261019)
+    T = 40
+
+    def spd(n, lo, hi):
+        Qm, _ = np.linalg.qr(rng.normal(size=(n, n)))
+        return Qm @ np.diag(rng.uniform(lo, hi, n)) @ Qm.T
+
+    AA = np.stack([0.9 * np.linalg.qr(rng.normal(size=(6, 6)))[0] + 0.08 * rng.normal(size=(6, 6)) for _ in range(T)], -1)
+    BB = 0.3 * rng.normal(size=(6, 2, T))
+    QQ = np.stack([spd(6, 0.1, 2.0) + np.triu(0.3 * rng.normal(size=(6, 6)), 1) for _ in range(T)], -1)
+    RR = np.stack([spd(2, 0.05, 1.0) for _ in range(T)], -1)
+    SS = 0.05 * rng.normal(size=(2, 6, T))
+    QQf = spd(6, 0.5, 5.0) + np.triu(0.5 * rng.normal(size=(6, 6)), 1)
+    x0 = rng.normal(0, 1, 6)
+    qq, rr, qqf = rng.normal(0, 1, (6, T)), rng.normal(0, 1, (2, T)), rng.normal(0, 1, 6)
+    assert not any(np.array_equal(QQ[:, :, t], QQ[:, :, t].T) for t in range(T)) and not np.array_equal(QQf, QQf.T)
+    nreg = {"n": 0}
+    orig = np.linalg.eigvals
+
+    def tap(M):
+        w = orig(M)
+        if not np.all(w > 0):
+            nreg["n"] += 1
+        return w
+
+    buf = io.StringIO()
+    np.linalg.eigvals = tap
+    try:
+        with contextlib.redirect_stdout(buf):
+            KK, PP, xx, uu = ref_opt.ltv_LQR(AA, BB, QQ, RR, SS, QQf, T, x0, qq, rr, qqf)
+    finally:
+        np.linalg.eigvals = orig
+    assert buf.getvalue() == "Augmented term!\n"
+    assert np.isfinite(KK).all() and np.isfinite(PP).all() and np.isfinite(xx).all()
+    print("  G14 ltv_nonsym T=%d regularised stages %d, max|KK| %.3g max|PP| %.3g, max|PP - PP^T| %.3g"
+          % (T, nreg["n"], np.abs(KK).max(), np.abs(PP).max(), np.abs(PP - PP.transpose(1, 0, 2)).max()))
+    save("g14_ltv_nonsym", AA=AA, BB=BB, QQ=QQ, RR=RR, SS=SS, QQf=QQf, x0=x0, qq=qq, rr=rr, qqf=qqf, TT=np.int64(T),
+         KK=KK, PP=PP, xx=xx.copy(), uu=uu.copy(), n_regularised=np.int64(nreg["n"]))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "dense":
+        return dense_vectors()
     if len(sys.argv) > 1 and sys.argv[1] == "gradient":
         return gradient_vectors()
     if len(sys.argv) > 1 and sys.argv[1] == "ltv_general":

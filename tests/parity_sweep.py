@@ -13,13 +13,15 @@ import numpy as np
 from oracle import oracle as orc
 
 
-def sweep(aoc, problems, B=4096, n_it=12, dist="random", prob="step", seed=4242, log=None, make_solver=None):
+def sweep(aoc, problems, B=4096, n_it=12, dist="random", prob="step", seed=4242, log=None, make_solver=None, weights=None):
     """make_solver(bp, B, prm) -> the solver under test (default: one NewtonBatchSolver; a TwoStreamNewtonSolver has the
-    same interface).  Which KERNELS it runs is decided by the batch size and aoc_tuning at the time of each iterate()."""
+    same interface).  Which KERNELS it runs is decided by the batch size and aoc_tuning at the time of each iterate().
+    weights: (QQt, RRt, QQT) in place of the problem's own (None: the driver's diagonal weights)."""
     # step maneuver at the bench's T = 500; the acrobatic problem at the reference's native T = 1000 (acrobatic_newton.py:72-76)
     pr = problems.step_maneuver(1.0, 2e-3) if prob == "step" else problems.acrobatic(1.0, 1e-3)
-    bp = aoc.BatchProblem(pr.QQt, pr.RRt, pr.QQT, pr.xx_ref, pr.uu_ref, pr.dt)
-    op = orc.OracleProblem(pr.QQt, pr.RRt, pr.QQT, pr.xx_ref, pr.uu_ref, pr.dt)
+    Q, R, QT = (pr.QQt, pr.RRt, pr.QQT) if weights is None else weights
+    bp = aoc.BatchProblem(Q, R, QT, pr.xx_ref, pr.uu_ref, pr.dt)
+    op = orc.OracleProblem(Q, R, QT, pr.xx_ref, pr.uu_ref, pr.dt)
     x0 = problems.random_x0(B, seed=seed) if dist == "random" else problems.perturbed_x0(pr, B, seed=seed)
     if prob == "acro" and dist == "random":
         x0[:, 2] = np.clip(x0[:, 2], 9.0, 12.0)

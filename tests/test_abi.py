@@ -124,6 +124,95 @@ def test_argument_errors_carry_a_reason():
     assert b"T = 2" in lib.aoc_last_hip_error()
 
 
+def _weights(p, Q, QT):
+    p.QQt[:] = [float(v) for v in Q.ravel()]
+    p.QQT[:] = [float(v) for v in QT.ravel()]
+    p.RRt[:] = [1e-6, 0.0, 0.0, 1e-6]
+
+
+def test_non_symmetric_state_weights_are_refused_where_the_riccati_recursion_runs():
+    """The Riccati kernels read one triangle of Q and Q_T: every entry point that runs the recursion
+    refuses a Q or Q_T with Q[i][j] != Q[j][i] before anything is launched, and names the matrix and the pair of
+    entries; a dense symmetric Q passes the check, and the entry points that are exact for any Q do not refuse it.
+    Every call is also invalid for a reason checked AFTER the weights (a NULL array, a workspace far too small, batch
+    sizes that differ), so a missing check is an error return with another reason, never a launch."""
+    import numpy as np
+    lib = _lib.lib()
+    rng = np.random.default_rng(7)
+    A = rng.normal(size=(6, 6)) * 1e-3
+    Qs = np.diag([1e-6, 0.1, 0.05, 0.01, 0.02, 1e-6]) + np.triu(A @ A.T) + np.triu(A @ A.T, 1).T   # dense, exactly symmetric
+    Qn = Qs.copy()
+    Qn[1, 4] += 1e-7                                                                                  # Q14 != Q41
+    QTn = Qs.copy()
+    QTn[5, 0] -= 1e-9                                                                                 # QT05 != QT50
+    p, q = _lib.Problem(), _lib.Problem()
+    for x in (p, q):
+        x.B, x.T, x.ref = 64, 10, 1
+        x.x_in_f32 = x.x_out_f32 = 1
+    prm = _lib.Params(200, 10, 1.0, 0.5, 0.7, -1e-6, 8, 0)
+    ws, ws32, wss = lib.aoc_workspace_bytes(64, 10), lib.aoc_workspace_bytes_f32(64, 10), lib.aoc_solve_workspace_bytes(64, 10)
+    P, Qp, M = C.byref(p), C.byref(q), C.byref(prm)
+    riccati = {
+        "aoc_backward": lambda: lib.aoc_backward(P, 0, None, 1, 1, 1, None, 1, None, 0),
+        "aoc_newton_iterate": lambda: lib.aoc_newton_iterate(P, M, 0, 1, 1, 1, 1, 1, ws // 100, 1, 1, 1, 1, 1, 1, 1),
+        "aoc_newton_iterate_f32": lambda: lib.aoc_newton_iterate_f32(P, M, 0, 1, 1, 1, 1, 1, ws32 // 100, 1, 1, 1, 1, 1, 1, 1),
+        "aoc_newton_solve": lambda: lib.aoc_newton_solve(P, M, 1, 1, 1, 1, wss // 100, 4, 1, 1, 1, 1, 1, None, None, None, None, None),
+        "aoc_newton_solve2": lambda: lib.aoc_newton_solve2(P, M, 1, 1, 1, 1, wss // 100, 4, 1, 1, 1, 1, 1, None, None, None, None,
+                                                           None, 1),
+        "aoc_lqr_tracking": lambda: lib.aoc_lqr_tracking(P, None, 1, 1, None, 1, None, None, 1),
+    }
+    # aoc_mpc_step: p = the tracking problem, q = the next problem; q.B != p.B is refused after both weight checks
+    mpc = lambda: lib.aoc_mpc_step(P, Qp, M, 1, *([1] * 6), 1 << 30, *([1] * 11), None, 1, None, None, None)
+    exact = {
+        "aoc_traj_cost": lambda: lib.aoc_traj_cost(P, None, 1, 1, 1),
+        "aoc_initial_trajectory": lambda: lib.aoc_initial_trajectory(P, 1.0, 1.0, None, 1, 1),
+        "aoc_rollout_cost": lambda: lib.aoc_rollout_cost(P, None, 1, None, None, 1, 1, 1, 1),
+        "aoc_gradient": lambda: lib.aoc_gradient(P, None, 1, 1, 1, 1, 1),
+        "aoc_forward": lambda: lib.aoc_forward(P, M, 2, None, 1, 1, 1, 1, 1, 1, 1, None, 0, None),
+        "aoc_linesearch_search": lambda: lib.aoc_linesearch_search(P, M, 2, None, 1, 1, 1, 1, 1, 1, 1, None, 0),
+    }
+
+    def other_reason():
+        # leave a reason that is not about the weights, so that a call refused for a NULL array (no new reason) shows
+        q2 = _lib.Problem()
+        q2.B, q2.T, q2.ref = 4, 2, 1
+        assert lib.aoc_traj_cost(C.byref(q2), 1, 1, 1, 1) == -1 and b"T = 2" in lib.aoc_last_hip_error()
+
+    def refused(call, name, matrix, i, j):
+        other_reason()
+        assert call() == -1, name
+        msg = lib.aoc_last_hip_error()
+        assert name.encode() in msg and b"not symmetric" in msg, (name, msg)
+        assert (b"%s[%d][%d]" % (matrix.encode(), i, j)) in msg and (b"%s[%d][%d]" % (matrix.encode(), j, i)) in msg, (name, msg)
+
+    def passed(call, name):
+        other_reason()
+        assert call() == -1, name
+        assert b"not symmetric" not in lib.aoc_last_hip_error(), (name, lib.aoc_last_hip_error())
+
+    for Q, QT, matrix, i, j in ((Qn, Qs, "QQt", 1, 4), (Qs, QTn, "QQT", 0, 5)):
+        _weights(p, Q, QT)
+        _weights(q, Qs, Qs)
+        q.B = 64 * 2
+        for name, call in riccati.items():
+            refused(call, name, matrix, i, j)
+        refused(mpc, "aoc_mpc_step (p_track)", matrix, i, j)
+        for name, call in exact.items():
+            passed(call, name)
+        _weights(p, Qs, Qs)                         # the next problem's weights are checked too
+        _weights(q, Q, QT)
+        refused(mpc, "aoc_mpc_step (p_next)", matrix, i, j)
+    # dense and symmetric: no entry point refuses it
+    _weights(p, Qs, Qs)
+    _weights(q, Qs, Qs)
+    for name, call in list(riccati.items()) + list(exact.items()) + [("aoc_mpc_step", mpc)]:
+        passed(call, name)
+    # the reason survives in full (the message buffer holds it)
+    _weights(p, Qn, Qs)
+    assert lib.aoc_backward(P, 0, None, 1, 1, 1, None, 1, None, 0) == -1
+    assert lib.aoc_last_hip_error().endswith(b"Q_T = Q_T^T")
+
+
 def test_too_small_a_workspace_is_an_error_not_a_fault():
     """aoc_newton_iterate / aoc_newton_solve / aoc_mpc_step are told the size of their workspace, aoc_forward /
     aoc_linesearch* the sizes of their scratch and candidate regions, and refuse one that is too small before anything

@@ -34,20 +34,26 @@ def test_f32_tolerance_sweep_acrobatic():
 
 def test_f32_matches_fp64_on_one_backward_forward():
     """One Newton iteration of the step-maneuver mini-batch in float32: same accepted steps as fp64
-    for the clear-cut first iterations, new cost within 1e-5."""
-    from conftest import load_golden
+    for the clear-cut first iterations, new cost within 1e-5.  Run with the driver's diagonal weights and with the
+    dense weights of test_gpu_dense.py (the only run of the float32 kernels built with DIAG = false), same gates."""
     from aircraftoptimalcontrol_amd import batch, problems
+    from test_gpu_dense import dense_weights
     pr = problems.step_maneuver(1.0, 2e-3)
-    bp = batch.BatchProblem(pr.QQt, pr.RRt, pr.QQT, pr.xx_ref, pr.uu_ref, pr.dt)
     x0 = problems.perturbed_x0(pr, 200, seed=11)
     prm = batch.make_params(stepsize_0=1.0, armijo_maxiters=10)
-    s64 = batch.NewtonBatchSolver(bp, 200, prm); s64.set_initial_from_x0(x0)
-    s32 = batch.NewtonBatchSolverF32(bp, 200, prm); s32.set_initial_from_x0(x0)
-    s64.iterate(0); s32.iterate(0)
-    a, b = s64.scalars(), s32.scalars()
-    assert np.allclose(b["cost"], a["cost"], rtol=2e-6) and np.allclose(b["cost_new"], a["cost_new"], rtol=1e-4)
-    assert np.allclose(b["descent"], a["descent"], rtol=1e-3)
-    assert np.mean(b["ntrials"] == a["ntrials"]) > 0.97
+    for Q, R, QT in ((pr.QQt, pr.RRt, pr.QQT), dense_weights(pr.QQt, pr.RRt, pr.QQT)):
+        bp = batch.BatchProblem(Q, R, QT, pr.xx_ref, pr.uu_ref, pr.dt)
+        s64 = batch.NewtonBatchSolver(bp, 200, prm); s64.set_initial_from_x0(x0)
+        s32 = batch.NewtonBatchSolverF32(bp, 200, prm); s32.set_initial_from_x0(x0)
+        s64.iterate(0); s32.iterate(0)
+        a, b = s64.scalars(), s32.scalars()
+        print("f32 vs fp64 (%s): cost %.3g, cost_new %.3g, descent %.3g rel max; ntrials equal %.4f" % (
+            "diagonal" if Q is pr.QQt else "dense", np.max(np.abs(b["cost"] / a["cost"] - 1)),
+            np.max(np.abs(b["cost_new"] / a["cost_new"] - 1)), np.max(np.abs(b["descent"] / a["descent"] - 1)),
+            np.mean(b["ntrials"] == a["ntrials"])))
+        assert np.allclose(b["cost"], a["cost"], rtol=2e-6) and np.allclose(b["cost_new"], a["cost_new"], rtol=1e-4)
+        assert np.allclose(b["descent"], a["descent"], rtol=1e-3)
+        assert np.mean(b["ntrials"] == a["ntrials"]) > 0.97
 
 
 def _acro_warm_start(B, seed=20260402):

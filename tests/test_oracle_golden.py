@@ -322,3 +322,49 @@ def test_g13_step_wide():
         r = orc.step(mdl, g["x"][i], g["u"][i], None, want3=True)
         assert rel_err(r[3], g["fxx3"][j], 1e-12) < 1e-12
         assert rel_err(r[5], g["fux3"][j], 1e-12) < 1e-12
+
+
+G14_CHAINS = ["g14_dense_step_T500", "g14_dense_nonsym_q_step_T500"]
+
+
+@pytest.mark.parametrize("chain", G14_CHAINS)
+def test_g14_dense_weights_chain_teacher_forced(chain):
+    """NewtonMethod with dense weights (make_golden.py dense): dense symmetric Q, R, Q_T, and the same with a
+    non-symmetric Q, on the step problem at T = 500, 11 iterations from the reference's initial guess (full Hessian from
+    kk = 9).  Each iteration is redone by the oracle from the reference's own iterate; the gates of
+    test_g6_chain_free_running: every Armijo step and trial count identical, cost within 1e-10 and descent within 1e-8,
+    states bit-identical and inputs within 1e-8 of their scale."""
+    g = load_golden(chain)
+    pr = load_golden("problem_step_T500")
+    p = orc.OracleProblem(g["QQt"], g["RRt"], g["QQT"], pr["xx_ref"], pr["uu_ref"], float(pr["dt"]))
+    assert np.array_equal(g["QQT"], g["QQT"].T) and np.array_equal(g["RRt"], g["RRt"].T)
+    assert np.array_equal(g["QQt"], g["QQt"].T) == (chain == "g14_dense_step_T500")
+    assert np.count_nonzero(g["QQt"] - np.diag(np.diag(g["QQt"]))) == 30      # dense
+    prm = orc.params()
+    n = int(g["n_done"])
+    assert n == 11 and len(g["stepsize"]) == n
+    xx, uu = g["xx_init"], g["uu_init"]
+    x0 = xx[:, 0].copy()
+    for kk in range(n):
+        r = orc.newton_iterate(p, prm, kk, xx, uu, x0)
+        assert abs(r["J"] - g["cost"][kk]) <= 1e-10 * abs(g["cost"][kk]), kk
+        assert abs(r["descent"] - g["descent"][kk]) <= 1e-8 * abs(g["descent"][kk]), kk
+        assert r["stepsize"] == g["stepsize"][kk] and r["ntrials"] == g["ntrials"][kk], kk
+        xx, uu = g["xx_it%d" % (kk + 1)], g["uu_it%d" % (kk + 1)]
+        assert np.array_equal(r["xx"], xx), "fp32-rounded states must match bit for bit (iter %d)" % kk
+        assert rel_err(r["uu"], uu, 1e-3) < 1e-8, kk
+
+
+def test_g14_ltv_lqr_non_symmetric_q():
+    """The generic ltv_LQR with a non-symmetric Q_t at every stage and a non-symmetric Qf (make_golden.py dense): the
+    gates of test_g12_ltv_lqr_general."""
+    g = load_golden("g14_ltv_nonsym")
+    assert not np.array_equal(g["QQf"], g["QQf"].T)
+    KK, PP, xx, uu, nreg, ns = orc.ltv_lqr(g["AA"], g["BB"], g["QQ"], g["RR"], g["SS"], g["QQf"], g["x0"], g["qq"], g["rr"],
+                                           g["qqf"])
+    assert ns == 0
+    assert nreg == int(g["n_regularised"])
+    tol = 1e-8 if nreg else 1e-10
+    for got, key in ((KK, "KK"), (PP, "PP"), (xx, "xx"), (uu, "uu")):
+        assert got.shape == g[key].shape, key
+        assert scaled_err(got, g[key]) < tol, (key, scaled_err(got, g[key]))
