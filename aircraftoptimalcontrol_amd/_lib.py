@@ -14,6 +14,7 @@ _SRC += sorted(os.path.join(_PKG, "csrc", "passes", f) for f in os.listdir(os.pa
 _HDR = os.path.join(os.path.dirname(_PKG), "include", "aoc.h")
 
 AOC_TILE = 64
+AOC_ENS_NSTAT = 16   # statistics per member of aoc_track_ensemble
 AOC_ABI_VERSION = 5   # include/aoc.h: the revision this binding (struct layouts, argument lists) is written against
 
 # status flags (include/aoc.h)
@@ -117,6 +118,7 @@ SYMBOLS = {
     "aoc_solve_trace": (C.c_int, [_P, _I]),
     "aoc_solve_trace_rows": (_I, []),
     "aoc_mpc_step": (C.c_int, [_P] * 3 + [_I] + [_P] * 6 + [_Z] + [_P] * 16),
+    "aoc_track_ensemble": (C.c_int, [_P, _I, _I] + [_P] * 8),
     "aoc_traj_cost_f32": (C.c_int, [_P] * 5),
     "aoc_initial_trajectory_f32": (C.c_int, [_P, _D, _D, _P, _P, _P]),
     "aoc_rollout_cost_f32": (C.c_int, [_P] * 9),

@@ -976,6 +976,137 @@ def lqr_tracking_batch(problem, xx_opt, uu_opt, delta):
     return unpack(xr, B).cpu().numpy(), unpack(ur, B).cpu().numpy(), KK, st[:B].cpu().numpy()
 
 
+# ------------------------------------------------------------------------------------------------
+# closed-loop tracking ensembles about shared optima (aoc_track_ensemble)
+# ------------------------------------------------------------------------------------------------
+ENS_REC = 20                       # doubles per stage record of `nominal`
+ENS_NSTAT = _lib.AOC_ENS_NSTAT     # statistics per member
+ENS_QUANTILES = (0.5, 0.9, 0.99)
+
+
+def ensemble_nominal(xx_opt, uu_opt, KK):
+    """The `nominal` array of aoc_track_ensemble on the host: xx_opt (n_opt,6,T), uu_opt (n_opt,2,T), KK (n_opt,2,6,T)
+    -> (n_opt,T,20) fp64, per sample x_opt[0..5], u_opt[0..1], K row 0 [0..5], K row 1 [0..5].  Needs no GPU."""
+    xo, uo, K = (np.asarray(a, dtype=np.float64) for a in (xx_opt, uu_opt, KK))
+    n, _, T = xo.shape
+    if xo.shape != (n, 6, T) or uo.shape != (n, 2, T) or K.shape != (n, 2, 6, T):
+        raise ValueError("xx_opt (n_opt,6,T), uu_opt (n_opt,2,T), KK (n_opt,2,6,T) expected, got %s %s %s"
+                         % (xo.shape, uo.shape, K.shape))
+    return np.ascontiguousarray(np.concatenate([xo, uo, K.reshape(n, 12, T)], axis=1).transpose(0, 2, 1))
+
+
+def ensemble_groups(B, n_opt, members_per_opt=None):
+    """How B members are dealt to n_opt optima: whole tiles, member b belongs to optimum b // members_per_opt.
+    members_per_opt=None: B spread evenly, rounded up to whole tiles.  -> (members_per_opt, group (B,) int).  Raises
+    ValueError where aoc_track_ensemble would refuse the geometry.  Needs no GPU."""
+    B, n_opt = int(B), int(n_opt)
+    if B < 1 or n_opt < 1:
+        raise ValueError("B = %d members, n_opt = %d optima" % (B, n_opt))
+    mpo = -(-(-(-B // n_opt)) // TILE) * TILE if members_per_opt is None else int(members_per_opt)
+    if mpo < TILE or mpo % TILE:
+        raise ValueError("members_per_opt = %d is not a positive multiple of %d" % (mpo, TILE))
+    if not (n_opt - 1) * mpo < B <= n_opt * mpo:
+        raise ValueError("B = %d members do not fill %d groups of %d (the last group may be partial, none empty)"
+                         % (B, n_opt, mpo))
+    return mpo, np.arange(B) // mpo
+
+
+def tracking_gains(problem, xx_opt, uu_opt):
+    """Tracking gains only (lqr_tracking.py:268-276) about n optima: ONE aoc_lqr_tracking call without the rollout.
+    xx_opt (n,6,T), uu_opt (n,2,T) -> KK (n,2,6,T) numpy, status (n,)."""
+    torch = _torch()
+    dev = problem.device
+    xx_opt = np.asarray(xx_opt, dtype=np.float64)
+    n, T = xx_opt.shape[0], problem.T
+    xt, ut = pack(xx_opt, dev), pack(uu_opt, dev)
+    xo0 = pack_vec(xx_opt[:, :, 0], dev)
+    Kg = alloc_tiled(n, T, 12, dev)
+    st = torch.zeros(ntiles(n) * TILE, dtype=torch.int32, device=dev)
+    p = problem.c_problem(n)
+    check(lib().aoc_lqr_tracking(C.byref(p), _ptr(xt), _ptr(ut), _ptr(xo0), None, _ptr(Kg), None, None, _ptr(st)),
+          "aoc_lqr_tracking")
+    return unpack(Kg, n).cpu().numpy().reshape(n, 2, 6, T), st[:n].cpu().numpy()
+
+
+def _ens_summary(torch, v):
+    """mean / max / quantiles over the members (rows) of one optimum, reduced on the device"""
+    q = torch.quantile(v, torch.tensor(ENS_QUANTILES, dtype=v.dtype, device=v.device), dim=0)
+    out = dict(mean=v.mean(dim=0), max=v.max(dim=0).values)
+    out.update({"q%02d" % round(100 * f): q[i] for i, f in enumerate(ENS_QUANTILES)})
+    return {k: a.cpu().numpy() for k, a in out.items()}
+
+
+def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, sigma=None, seed=20260405, first=0,
+                   step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True):
+    """Closed-loop tracking ensemble about shared optima (aoc_track_ensemble): the loop of lqr_tracking.py:279-281 for B
+    members, u_t = u_opt_t + K_t (x_t - x_opt_t), x_{t+1} = step(x_t, u_t) + d_t, reduced to per-member statistics on
+    the device; the optimum and its gains are stored once per optimum, not once per member.
+    problem: BatchProblem with the tracking weights (lqr_tracking.py:324-328): they weigh the gains (KK=None) and the
+    cost statistic.  xx_opt (6,T) or (n_opt,6,T), uu_opt likewise.  Members: x0_reg (B,6), or delta (B,6) added to sample
+    0 of each member's optimum (lqr_tracking.py:265); member b belongs to optimum b // members_per_opt (ensemble_groups).
+    KK=None: gains from ONE aoc_lqr_tracking call on the n_opt optima; KK (n_opt,2,6,T) (or (2,6,T)): used as is.
+    sigma (6,) or None: std of the disturbance d_t drawn on the device, a function of (seed, first + b, step0 + t) —
+    mpc.noise_draws(seed, step0 + t, first, B, sigma) restates it.  trajectories: also return xx_reg (B,6,T) (f32:
+    stored as float32 on the device; not with sigma), uu_reg (B,2,T), dist (B,6,T) — numpy, or device tensors with
+    to_host=False.
+    Returns dict(max_dx (B,6), max_du (B,2), cost (B,), final_dx (B,6), first_bad (B,) int, status (B,), stats (B,16),
+    members_per_opt, group (B,), summary: per optimum dict(n, n_bad = members with first_bad < T, max_dx / final_dx /
+    cost: mean, max, q50, q90, q99 over the members — final_dx signed —, reduced with torch on the device))."""
+    torch = _torch()
+    dev = problem.device
+    xo, uo = np.asarray(xx_opt, dtype=np.float64), np.asarray(uu_opt, dtype=np.float64)
+    if xo.ndim == 2:
+        xo, uo = xo[None], uo[None]
+    n_opt, T = xo.shape[0], problem.T
+    if xo.shape != (n_opt, 6, T) or uo.shape != (n_opt, 2, T):
+        raise ValueError("xx_opt must be (6,T) or (n_opt,6,T) with T = %d, uu_opt likewise" % T)
+    if (x0_reg is None) == (delta is None):
+        raise ValueError("give the members either as x0_reg (B,6) or as delta (B,6)")
+    m = np.asarray(x0_reg if delta is None else delta, dtype=np.float64)
+    if m.ndim != 2 or m.shape[1] != 6:
+        raise ValueError("x0_reg / delta must be (B,6)")
+    B = m.shape[0]
+    mpo, group = ensemble_groups(B, n_opt, members_per_opt)
+    x0 = m if delta is None else xo[group, :, 0] + m
+    if KK is None:
+        KK, _ = tracking_gains(problem, xo, uo)
+    else:
+        KK = np.asarray(KK, dtype=np.float64)
+        KK = KK[None] if KK.ndim == 3 else KK
+    nominal = torch.from_numpy(ensemble_nominal(xo, uo, KK)).to(dev)
+    x0t = pack_vec(x0, dev)
+    nt = ntiles(B)
+    stats = torch.empty((nt, ENS_NSTAT, TILE), dtype=torch.float64, device=dev)
+    status = torch.zeros(nt * TILE, dtype=torch.int32, device=dev)
+    xr = ur = ds = None
+    if trajectories:
+        xr, ur = alloc_tiled(B, T, 6, dev, f32=f32), alloc_tiled(B, T, 2, dev)
+        ds = alloc_tiled(B, T, 6, dev)
+    nz = None
+    if sigma is not None:
+        nz = _lib.MpcNoise(int(seed), int(step0), int(first), (C.c_double * 6)(*np.asarray(sigma, dtype=np.float64).tolist()))
+    p = problem.c_problem(B, x_out_f32=int(bool(f32)))
+    check(lib().aoc_track_ensemble(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), C.byref(nz) if nz is not None else None,
+                                   _ptr(xr), _ptr(ur), _ptr(ds), _ptr(stats), _ptr(status)), "aoc_track_ensemble")
+    sv = unpack_vec(stats, B)                                   # (B,16) on the device
+    first_bad = sv[:, 15].to(torch.int64)
+    summary = []
+    for g in range(n_opt):
+        sl = slice(g * mpo, min((g + 1) * mpo, B))
+        summary.append(dict(n=sl.stop - sl.start, n_bad=int((first_bad[sl] < T).sum()),
+                            max_dx=_ens_summary(torch, sv[sl, 0:6]), final_dx=_ens_summary(torch, sv[sl, 9:15]),
+                            cost=_ens_summary(torch, sv[sl, 8])))
+    s = sv.cpu().numpy()
+    out = dict(max_dx=s[:, 0:6], max_du=s[:, 6:8], cost=s[:, 8], final_dx=s[:, 9:15], first_bad=s[:, 15].astype(np.int64),
+               status=status[:B].cpu().numpy(), stats=s, members_per_opt=mpo, group=group, summary=summary)
+    if trajectories:
+        xd = unpack(xr, B)
+        xd[:, :, 0] = _dev_f64(x0, dev)                         # sample 0 is the fp64 x0, as everywhere
+        host = (lambda t: t.cpu().numpy()) if to_host else (lambda t: t)
+        out.update(xx_reg=host(xd), uu_reg=host(unpack(ur, B)), dist=host(unpack(ds, B)))
+    return out
+
+
 def ltv_lqr_batch(AA, BB, QQ, RR, SS, QQf, x0, qq=None, rr=None, qqf=None, device="cuda:0"):
     """Generic ltv_LQR for nb problems (reference optcon.py:533-771).  Time-major inputs per problem:
     AA (nb,T,6,6), BB (nb,T,6,2), QQ (nb,T,6,6), RR (nb,T,2,2), SS (nb,T,2,6), QQf (nb,6,6), x0 (nb,6),

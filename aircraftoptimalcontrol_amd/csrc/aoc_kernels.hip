@@ -7,7 +7,7 @@
 // No MFMA (the blocks are 6x6/6x2); the per-lane state (P: 21, p: 6, lambda: 6 doubles, ...) lives in VGPRs.
 // The kernels themselves are in aoc_passes.inc (which includes passes/*.inc, one file per pass: layout, unit, cost_rollout,
 // backward, forward, tracking, hcut, ltv_lqr, linesearch, mpc; then the launch functions api.inc and the solve loop
-// solve.inc) + aoc_device.h, compiled twice: fp64 (aoc64, the parity path) and float32 (aoc32, BASELINE config 3); this file
+// solve.inc, and ensemble.inc with its own launch function) + aoc_device.h, compiled twice: fp64 (aoc64, the parity path) and float32 (aoc32, BASELINE config 3); this file
 // holds what is common and the C-ABI.
 #include <hip/hip_runtime.h>
 
@@ -515,6 +515,13 @@ int aoc_mpc_step(const aoc_problem* p_track, const aoc_problem* p_next, const ao
     return aoc64::api_mpc_step(p_track, p_next, prm, n_newton, x_cur, u_cur, x0, x_true, disturbance, workspace, workspace_bytes, Kgain, x_a,
                                u_a, x_b, u_b, J_a, J_b, descent, stepsize, ntrials, status, K0, u_applied, final_slot, noise,
                                disturbance_out);
+}
+
+int aoc_track_ensemble(const aoc_problem* p, int32_t n_opt, int32_t members_per_opt, const double* nominal,
+                       const double* x0_reg, const aoc_mpc_noise* noise, void* x_reg, double* u_reg, double* dist_out,
+                       double* stats, int32_t* status) {
+    static_assert(aoc64::ENS_NSTAT == AOC_ENS_NSTAT, "stats rows of the kernel and of the header");
+    return aoc64::api_track_ensemble(p, n_opt, members_per_opt, nominal, x0_reg, noise, x_reg, u_reg, dist_out, stats, status);
 }
 
 // ---- float32 arithmetic (aoc32): every array, the reference curves and the workspace are float32 ------

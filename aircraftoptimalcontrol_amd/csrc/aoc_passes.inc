@@ -20,5 +20,6 @@ namespace AOC_ARITH_NS {
 #include "passes/api.inc"
 #include "passes/solve.inc"
 #endif  // AOC_KERNELS_ONLY
+#include "passes/ensemble.inc"   // kernel and launch function in one file (the latter uses make_const of api.inc)
 
 }  // namespace AOC_ARITH_NS

@@ -1,0 +1,44 @@
+#!/usr/bin/env python3
+"""Closed-loop tracking ensemble about a saved optimum (the robustness sample of lqr_tracking.py:245-283, many times over):
+loads Data/xx_star.npy, Data/uu_star.npy (what run_newton.py writes), computes the tracking gains once, rolls out
+--members perturbed and disturbed closed loops on the device and prints the distribution of the tracking errors as one
+JSON line.
+
+    python examples/run_tracking_ensemble.py [--data Data] [--members 65536] [--sigma 1e-3 1e-3 1e-2 1e-4 1e-3 1e-4]
+                                             [--delta 0.3 0.3 0.5 0.05 0.1 0.05] [--seed 1] [--dt 1e-3]
+"""
+import argparse
+import json
+import os
+
+import numpy as np
+
+import _common  # noqa: F401
+from aircraftoptimalcontrol_amd import batch, problems
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--data", default="Data")
+    ap.add_argument("--members", type=int, default=65536)
+    ap.add_argument("--sigma", type=float, nargs=6, default=None, help="std of the state disturbance per step (default: none)")
+    ap.add_argument("--delta", type=float, nargs=6, default=[0.3, 0.3, 0.5, 0.05, 0.1, 0.05],
+                    help="std of the perturbation of the initial state")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dt", type=float, default=1e-3)
+    a = ap.parse_args()
+    xx_opt = np.load(os.path.join(a.data, "xx_star.npy"))
+    uu_opt = np.load(os.path.join(a.data, "uu_star.npy"))
+    T = xx_opt.shape[1]
+    Q, R, QT = problems.tracking_weights()                           # lqr_tracking.py:324-328
+    bp = batch.BatchProblem(Q, R, QT, np.zeros((6, T)), np.zeros((2, T)), a.dt)
+    delta = np.random.default_rng(a.seed).normal(size=(a.members, 6)) * np.asarray(a.delta)
+    r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed)
+    sm = r["summary"][0]
+    tolist = lambda d: {k: np.asarray(v).tolist() for k, v in d.items()}
+    print(json.dumps(dict(members=a.members, T=T, sigma=a.sigma, left_the_domain=sm["n_bad"],
+                          max_dx=tolist(sm["max_dx"]), final_dx=tolist(sm["final_dx"]), cost=tolist(sm["cost"]))))
+
+
+if __name__ == "__main__":
+    main()

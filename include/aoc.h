@@ -57,7 +57,8 @@ extern "C" {
  *      search (armijo_maxiters + 1 where every candidate rides along)
  *   5: aoc_mpc_step takes aoc_mpc_noise (the disturbance drawn on the device) and disturbance_out; the horizon cut is
  *      decided once per aoc_newton_solve from the caller's batch (a trajectory's bits no longer depend on the generation or
- *      half it is solved in); aoc_tuning.fw_wpe1, hcut_chain6, bw_hcut_full, fw_duo, hcut_waves, hcut_pairs */
+ *      half it is solved in); aoc_tuning.fw_wpe1, hcut_chain6, bw_hcut_full, fw_duo, hcut_waves, hcut_pairs
+ *      (still 5, an addition: aoc_track_ensemble — no struct, argument list or size query changed) */
 #define AOC_ABI_VERSION 5
 
 #define AOC_TILE 64
@@ -489,6 +490,41 @@ int aoc_mpc_step(const aoc_problem *prob_track, const aoc_problem *prob_next, co
                  double *u_b, double *J_a, double *J_b, double *descent, double *stepsize, int32_t *ntrials,
                  int32_t *status, double *K0, double *u_applied, int32_t *final_slot, const aoc_mpc_noise *noise,
                  double *disturbance_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Closed-loop tracking ensemble about a shared optimum: the loop of lqr_tracking.py:279-281 for B members that share
+ * n_opt optima — u_t = u_opt_t + K_t (x_t - x_opt_t), x_{t+1} = Dynamics.step(x_t, u_t) + d_t for t = 0 .. T-2, in the
+ * arithmetic of aoc_lqr_tracking's rollout (bit-identical to it where no disturbance is drawn) — without replicating
+ * the optimum and the gains per member, and reduced to per-member statistics on the device.
+ * prob: model (incl. dt), T, B = members in total, QQt/RRt/QQT = weights of the tracking-cost statistic (any matrices, as
+ *   for aoc_traj_cost; RRt symmetric), x_out_f32 = element type of x_reg, stream.  ref, ref_per_traj, x_in_f32 and
+ *   x_is_rollout are not read.
+ * nominal: DEVICE, fp64, [n_opt][T][20]: per sample x_opt[0..5], u_opt[0..1], K row 0 [0..5], K row 1 [0..5] (sample T-1:
+ *   only x_opt is used) — one 160-byte record per stage, shared by every member of the optimum.
+ * Members are grouped by tile: members_per_opt is a positive multiple of 64, tile i belongs to optimum
+ *   i / (members_per_opt / 64), and (n_opt-1)*members_per_opt < B <= n_opt*members_per_opt.  Lanes of the last tile beyond
+ *   B replicate member B-1.
+ * x0_reg: [ntiles][6][64], each member's initial state (lqr_tracking.py:265 generalised).
+ * noise (HOST pointer, may be NULL = no disturbance): d_t of member b is the draw of aoc_mpc_step's generator with key =
+ *   seed and counter (noise->first + b, noise->step + t, c/2, 0), component c scaled by sigma[c]: a function of (seed,
+ *   global member index, step) alone, so the draws do not depend on how an ensemble is cut into calls.  Disturbed states
+ *   are arbitrary fp64 values: x_out_f32 = 1 together with x_reg and noise is AOC_EINVAL.
+ * Outputs, each may be NULL except stats (x_reg and u_reg go together): x_reg (tiled C=6; sample 0 is x0_reg, rounded if
+ *   float32), u_reg (tiled C=2, sample T-1 zero), dist_out (tiled C=6: sample t = what was added to form x_{t+1}, sample
+ *   T-1 zero), status (OR-ed: AOC_ST_VNONPOS if !(V_t > 0) at a stage t <= T-2, as aoc_lqr_tracking's rollout flags it;
+ *   AOC_ST_NAN if any state sample is not finite).
+ * stats: [ntiles][AOC_ENS_NSTAT][64] fp64 per member:
+ *   0-5   max over t = 0..T-1 of |x_t[c] - x_opt_t[c]|        6-7  max over t = 0..T-2 of |u_t[c] - u_opt_t[c]|
+ *         (a NaN sticks in both)
+ *   8     cost of (x_reg, u_reg) about the optimum with prob's weights — the bits aoc_traj_cost gives with ref = (x_opt, u_opt)
+ *   9-14  x_{T-1}[c] - x_opt_{T-1}[c]
+ *   15    first sample index at which !(V > 0) or a state component is not finite; T if none.
+ * One wavefront per tile: 65 536 members fill the device; below ~16 384 the call is latency-bound on lone wavefronts.
+ * --------------------------------------------------------------------------------------------- */
+#define AOC_ENS_NSTAT 16
+int aoc_track_ensemble(const aoc_problem *prob, int32_t n_opt, int32_t members_per_opt, const double *nominal,
+                       const double *x0_reg, const aoc_mpc_noise *noise, void *x_reg, double *u_reg, double *dist_out,
+                       double *stats, int32_t *status);
 
 /* ---------------------------------------------------------------------------------------------
  * float32 arithmetic (BASELINE.json configs[2]: "fp32 with tolerance sweep").

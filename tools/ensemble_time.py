@@ -1,0 +1,174 @@
+#!/usr/bin/env python3
+"""Closed-loop tracking ensemble about ONE optimum: aoc_track_ensemble against the replicated path it replaces.
+
+    python tools/ensemble_time.py [--members 65536 262144] [--T 1000] [--seconds 0.5] [--repeats 3] [--out FILE]
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/ensemble_time.py --trace --members N
+    python tools/ensemble_time.py --kernel-times DIR                 (kernel times: a traced run of its own, then its summary)
+
+  A          aoc_lqr_tracking on the optimum replicated per member (gains + closed-loop rollout; states float32 in and out,
+             the cheapest form of that path); its rollout kernel alone is k_track_rollout in the kernel trace
+  B_stats    aoc_track_ensemble, statistics only         B_traj   ... writing x_reg (float32) and u_reg
+  B_noise    ... statistics only, with the disturbance drawn on the device
+The optimum is the g4 fixture's (T = 1000; --T cuts it), the members are seeded perturbations of its first sample.
+Profiler off: HIP events around at least --seconds of back-to-back launches per variant, after a warm-up of every variant;
+the variants take turns inside each of --repeats rounds, so that a drift of the machine hits all of them.  One JSON line:
+per size and variant the ms per call of every round, B/A, member-stages per second, and — from --valu, the vector
+instructions of one stage on the executed path of the ISA (tools/one_kernel.sh, tools/isa_loops.py) — the share of the fp64
+vector-issue roof (1024 SIMDs, one instruction per 4 cycles at 2.4 GHz): this kernel's bound is issue, not HBM.
+--trace: three calls per variant and size and nothing else, for the kernel trace; --kernel-times DIR (no GPU) then reads
+the *kernel_trace.csv under DIR and prints per tracking kernel its durations, their median and spread.  An allocation the
+device refuses is reported for that size, never shrunk."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+SIMDS, CYCLES_PER_VALU, CLOCK_HZ = 1024, 4, 2.4e9
+DELTA_SCALE = np.array([0.3, 0.3, 0.5, 0.05, 0.1, 0.05])
+SIGMA = np.array([1e-3, 1e-3, 1e-2, 1e-4, 1e-3, 1e-4])
+
+
+def setup(B, T, g):
+    """Device buffers and the four launch closures for B members."""
+    import torch
+    from aircraftoptimalcontrol_amd import _lib, batch
+    from aircraftoptimalcontrol_amd.batch import TILE, _ptr, alloc_tiled, check, lib, ntiles, pack, pack_vec
+    dev = torch.device("cuda:0")
+    xo, uo = g["xx_opt"][:, :T], g["uu_opt"][:, :T]
+    bp = batch.BatchProblem(g["QQt"], g["RRt"], g["QQT"], np.zeros((6, T)), np.zeros((2, T)), float(g["dt"]), device=dev)
+    nt = ntiles(B)
+    rng = np.random.default_rng(3)
+    x0 = xo[:, 0] + rng.normal(size=(B, 6)) * DELTA_SCALE
+    x0t = pack_vec(x0, dev)
+    status = torch.zeros(nt * TILE, dtype=torch.int32, device=dev)
+    # A: one tile of the optimum, replicated over the tiles on the device
+    rep = lambda a, f32=False: pack(np.repeat(a[None], TILE, 0), dev, f32=f32).expand(nt, -1, -1, -1).contiguous()
+    xt, ut = rep(xo, True), rep(uo)
+    xo0 = pack_vec(np.repeat(xo[:, 0][None], B, 0), dev)
+    Kg = alloc_tiled(B, T, 12, dev)
+    xr, ur = alloc_tiled(B, T, 6, dev, f32=True), alloc_tiled(B, T, 2, dev)
+    pA = bp.c_problem(B, x_in_f32=1, x_out_f32=1)
+
+    def run_A():
+        check(lib().aoc_lqr_tracking(C.byref(pA), _ptr(xt), _ptr(ut), _ptr(xo0), _ptr(x0t), _ptr(Kg), _ptr(xr), _ptr(ur),
+                                     _ptr(status)), "aoc_lqr_tracking")
+
+    # B: the gains of ONE trajectory, the nominal once
+    KK, _ = batch.tracking_gains(bp, xo[None], uo[None])
+    nominal = torch.from_numpy(batch.ensemble_nominal(xo[None], uo[None], KK)).to(dev)
+    stats = torch.empty((nt, batch.ENS_NSTAT, TILE), dtype=torch.float64, device=dev)
+    nz = _lib.MpcNoise(20261016, 0, 0, (C.c_double * 6)(*SIGMA.tolist()))
+    pB = bp.c_problem(B, x_out_f32=1)
+
+    def run_B(traj=False, noise=False):
+        check(lib().aoc_track_ensemble(C.byref(pB), 1, nt * TILE, _ptr(nominal), _ptr(x0t), C.byref(nz) if noise else None,
+                                       _ptr(xr) if traj else None, _ptr(ur) if traj else None, None, _ptr(stats),
+                                       _ptr(status)), "aoc_track_ensemble")
+
+    return dict(A=run_A, B_stats=run_B, B_traj=lambda: run_B(traj=True), B_noise=lambda: run_B(noise=True))
+
+
+def timed(fn, seconds):
+    """ms per call over at least `seconds` of back-to-back launches (HIP events; one launch first sizes the window)"""
+    import torch
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record(); fn(); ev[1].record(); torch.cuda.synchronize()
+    n = max(2, int(np.ceil(seconds * 1e3 / max(ev[0].elapsed_time(ev[1]), 1e-3))))
+    ev[0].record()
+    for _ in range(n):
+        fn()
+    ev[1].record(); torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]) / n, n
+
+
+def kernel_times(d):
+    """Durations [ms] of the tracking kernels in the rocprofv3 kernel trace(s) under d, in launch order: *kernel_trace.csv
+    (--output-format csv) or the *_results.db this rocprofv3 writes by default (its `kernels` view)."""
+    import collections
+    import csv
+    import glob
+    import sqlite3
+    rows = []
+    for f in sorted(glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)):
+        rows += [(r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Grid_Size_X", r.get("Grid_Size", "?")))
+                 for r in csv.DictReader(open(f))]
+    if not rows:
+        for f in sorted(glob.glob(os.path.join(d, "**", "*_results.db"), recursive=True)):
+            rows += list(sqlite3.connect(f).execute("select name, start, end, grid_x from kernels"))
+    out = collections.OrderedDict()
+    for name, t0, t1, grid in sorted(rows, key=lambda r: r[1]):
+        name = name.split("(")[0].replace("void ", "").replace("aoc64::", "")
+        if name.startswith("k_track_"):
+            out.setdefault("%s grid=%s" % (name, grid), []).append(round((t1 - t0) / 1e6, 4))
+    for k, v in out.items():
+        print(json.dumps(dict(kernel=k, ms=v, median=float(np.median(v)), spread_rel=round((max(v) - min(v)) / float(np.median(v)), 4))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--members", type=int, nargs="+", default=[65536, 262144])
+    ap.add_argument("--T", type=int, default=1000)
+    ap.add_argument("--seconds", type=float, default=0.5)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--valu", type=int, default=0, help="vector instructions per stage of the stats-only kernel (from the ISA)")
+    ap.add_argument("--trace", action="store_true", help="three calls per variant and nothing else (under rocprofv3)")
+    ap.add_argument("--kernel-times", default=None, metavar="DIR", help="summarise the kernel trace(s) under DIR (no GPU)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.kernel_times:
+        return kernel_times(a.kernel_times)
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("ensemble_time.py needs the GPU: there is nothing to time without one")
+    g = dict(np.load(os.path.join(ROOT, "tests", "golden", "g4_lqr_tracking.npz"), allow_pickle=False))
+    out = dict(T=a.T, seconds=a.seconds, sizes=[])
+    for B in a.members:
+        rec = dict(members=B)
+        try:
+            runs = setup(B, a.T, g)
+        except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
+            rec["refused"] = "allocation refused: %s" % str(e).split("\n")[0]
+            out["sizes"].append(rec)
+            continue
+        for fn in runs.values():          # warm-up: code objects, allocator
+            fn()
+        torch.cuda.synchronize()
+        if a.trace:
+            for fn in runs.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            rec["trace_calls_per_variant"] = 4
+        else:
+            ms = {k: [] for k in runs}
+            for _ in range(a.repeats):
+                for k, fn in runs.items():
+                    ms[k].append(round(timed(fn, a.seconds)[0], 4))
+            rec["ms"] = ms
+            med = {k: float(np.median(v)) for k, v in ms.items()}
+            rec["A_spread_rel"] = round((max(ms["A"]) - min(ms["A"])) / med["A"], 4)
+            rec["B_over_A"] = {k: round(med[k] / med["A"], 4) for k in ms if k != "A"}
+            stages = B * (a.T - 1)
+            rec["member_stages_per_s"] = {k: round(stages / (med[k] * 1e-3), 0) for k in ms}
+            if a.valu:
+                roof_ms = (B / 64) * (a.T - 1) * a.valu * CYCLES_PER_VALU / (SIMDS * CLOCK_HZ) * 1e3
+                rec["vector_issue"] = dict(valu_per_stage=a.valu, roof_ms=round(roof_ms, 4),
+                                           share_B_stats=round(roof_ms / med["B_stats"], 3), bound="issue")
+        out["sizes"].append(rec)
+        del runs
+        torch.cuda.empty_cache()
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
