@@ -982,6 +982,12 @@ def lqr_tracking_batch(problem, xx_opt, uu_opt, delta):
 ENS_REC = 20                       # doubles per stage record of `nominal`
 ENS_NSTAT = _lib.AOC_ENS_NSTAT     # statistics per member
 ENS_QUANTILES = (0.5, 0.9, 0.99)
+ENV_NREC = _lib.AOC_ENV_NREC       # doubles per (optimum, sample) record of aoc_track_ensemble_envelope
+# the record (include/aoc.h): n | min dx | max dx | min du | max du | sum dx | sum dx_i dx_j (upper triangle, row by row)
+_ENV_MIN = np.r_[1:7, 13:15]
+_ENV_MAX = np.r_[7:13, 15:17]
+_ENV_SUM = np.r_[0:1, 17:44]
+_ENV_TRI = np.triu_indices(6)
 
 
 def ensemble_nominal(xx_opt, uu_opt, KK):
@@ -1028,6 +1034,43 @@ def tracking_gains(problem, xx_opt, uu_opt):
     return unpack(Kg, n).cpu().numpy().reshape(n, 2, 6, T), st[:n].cpu().numpy()
 
 
+def envelope_merge(raw_a, raw_b):
+    """Records (..., 44) of two disjoint sets of members of the same optimum -> the record of their union: n and the sums
+    add, the minima and maxima combine.  What joins calls cut by `first=`, and what a multi-GPU job all-reduces (SUM for
+    0 and 17-43, MIN for 1-6 and 13-14, MAX for 7-12 and 15-16).  NumPy only, needs no GPU."""
+    a, b = np.asarray(raw_a, dtype=np.float64), np.asarray(raw_b, dtype=np.float64)
+    if a.shape != b.shape or a.shape[-1] != ENV_NREC:
+        raise ValueError("two arrays of records (..., %d) of one shape expected, got %s %s" % (ENV_NREC, a.shape, b.shape))
+    out = np.empty_like(a)
+    out[..., _ENV_SUM] = a[..., _ENV_SUM] + b[..., _ENV_SUM]
+    out[..., _ENV_MIN] = np.minimum(a[..., _ENV_MIN], b[..., _ENV_MIN])
+    out[..., _ENV_MAX] = np.maximum(a[..., _ENV_MAX], b[..., _ENV_MAX])
+    return out
+
+
+def envelope_moments(raw):
+    """Records (T, 44) -> n (T,) int, mean_dx (6,T), cov_dx (6,6,T): the population covariance E[dx dx^T] - E[dx] E[dx]^T
+    from the raw moments; mean and covariance are NaN where n = 0.  NumPy only, needs no GPU."""
+    raw = np.asarray(raw, dtype=np.float64)
+    if raw.ndim != 2 or raw.shape[1] != ENV_NREC:
+        raise ValueError("records (T, %d) expected, got %s" % (ENV_NREC, raw.shape))
+    n = raw[:, 0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(n[:, None] > 0, raw[:, 17:23] / n[:, None], np.nan)           # (T,6)
+        second = np.empty((raw.shape[0], 6, 6))
+        second[:, _ENV_TRI[0], _ENV_TRI[1]] = raw[:, 23:44]
+        second[:, _ENV_TRI[1], _ENV_TRI[0]] = raw[:, 23:44]
+        second = np.where(n[:, None, None] > 0, second / n[:, None, None], np.nan)
+    cov = second - mean[:, :, None] * mean[:, None, :]
+    return n.astype(np.int64), np.ascontiguousarray(mean.T), np.ascontiguousarray(cov.transpose(1, 2, 0))
+
+
+def _envelope_dict(raw):
+    n, mean, cov = envelope_moments(raw)
+    return dict(n=n, min_dx=raw[:, 1:7].T.copy(), max_dx=raw[:, 7:13].T.copy(), min_du=raw[:, 13:15].T.copy(),
+                max_du=raw[:, 15:17].T.copy(), mean_dx=mean, cov_dx=cov, raw=raw)
+
+
 def _ens_summary(torch, v):
     """mean / max / quantiles over the members (rows) of one optimum, reduced on the device"""
     q = torch.quantile(v, torch.tensor(ENS_QUANTILES, dtype=v.dtype, device=v.device), dim=0)
@@ -1037,7 +1080,7 @@ def _ens_summary(torch, v):
 
 
 def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, sigma=None, seed=20260405, first=0,
-                   step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True):
+                   step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True, envelope=False):
     """Closed-loop tracking ensemble about shared optima (aoc_track_ensemble): the loop of lqr_tracking.py:279-281 for B
     members, u_t = u_opt_t + K_t (x_t - x_opt_t), x_{t+1} = step(x_t, u_t) + d_t, reduced to per-member statistics on
     the device; the optimum and its gains are stored once per optimum, not once per member.
@@ -1051,7 +1094,11 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     to_host=False.
     Returns dict(max_dx (B,6), max_du (B,2), cost (B,), final_dx (B,6), first_bad (B,) int, status (B,), stats (B,16),
     members_per_opt, group (B,), summary: per optimum dict(n, n_bad = members with first_bad < T, max_dx / final_dx /
-    cost: mean, max, q50, q90, q99 over the members — final_dx signed —, reduced with torch on the device))."""
+    cost: mean, max, q50, q90, q99 over the members — final_dx signed —, reduced with torch on the device)).
+    envelope=True (aoc_track_ensemble_envelope; every other output keeps its bits): also `envelope`, per optimum the
+    reduction over its members at every sample, dict(n (T,) int = members still in the domain, min_dx / max_dx (6,T),
+    min_du / max_du (2,T; sample T-1: +inf / -inf), mean_dx (6,T), cov_dx (6,6,T) (population covariance; NaN where
+    n = 0), raw (T,44) = the device's record, see envelope_merge / envelope_moments)."""
     torch = _torch()
     dev = problem.device
     xo, uo = np.asarray(xx_opt, dtype=np.float64), np.asarray(uu_opt, dtype=np.float64)
@@ -1086,8 +1133,17 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     if sigma is not None:
         nz = _lib.MpcNoise(int(seed), int(step0), int(first), (C.c_double * 6)(*np.asarray(sigma, dtype=np.float64).tolist()))
     p = problem.c_problem(B, x_out_f32=int(bool(f32)))
-    check(lib().aoc_track_ensemble(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), C.byref(nz) if nz is not None else None,
-                                   _ptr(xr), _ptr(ur), _ptr(ds), _ptr(stats), _ptr(status)), "aoc_track_ensemble")
+    nzp = C.byref(nz) if nz is not None else None
+    if envelope:
+        env = torch.empty((n_opt, T, ENV_NREC), dtype=torch.float64, device=dev)
+        nbytes = int(lib().aoc_ensemble_envelope_scratch_bytes(B, T, mpo))
+        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+        check(lib().aoc_track_ensemble_envelope(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp, _ptr(xr), _ptr(ur),
+                                                _ptr(ds), _ptr(stats), _ptr(status), _ptr(env), _ptr(scratch), nbytes),
+              "aoc_track_ensemble_envelope")
+    else:
+        check(lib().aoc_track_ensemble(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp,
+                                       _ptr(xr), _ptr(ur), _ptr(ds), _ptr(stats), _ptr(status)), "aoc_track_ensemble")
     sv = unpack_vec(stats, B)                                   # (B,16) on the device
     first_bad = sv[:, 15].to(torch.int64)
     summary = []
@@ -1099,6 +1155,8 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     s = sv.cpu().numpy()
     out = dict(max_dx=s[:, 0:6], max_du=s[:, 6:8], cost=s[:, 8], final_dx=s[:, 9:15], first_bad=s[:, 15].astype(np.int64),
                status=status[:B].cpu().numpy(), stats=s, members_per_opt=mpo, group=group, summary=summary)
+    if envelope:
+        out["envelope"] = [_envelope_dict(r) for r in env.cpu().numpy()]
     if trajectories:
         xd = unpack(xr, B)
         xd[:, :, 0] = _dev_f64(x0, dev)                         # sample 0 is the fp64 x0, as everywhere

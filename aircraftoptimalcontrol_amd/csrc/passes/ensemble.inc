@@ -21,6 +21,56 @@ constexpr int ENS_BLK = 16;     // stage records per cooperative load
 constexpr int ENS_PF = ENS_BLK * ENS_REC / TILE;   // doubles per lane and block
 static_assert(ENS_PF * TILE == ENS_BLK * ENS_REC, "a block of records is a whole number of doubles per lane");
 
+// ---- per-stage envelope over the members (aoc_track_ensemble_envelope) ----------------------------------------------
+// Record of one (optimum, sample): n, min / max of dx[6] and du[2], sum dx[6], sum dx_i dx_j (i <= j), AOC_ENV_NREC = 44
+// doubles (include/aoc.h).  The ENV instances of k_track_ensemble stage ENV_S samples at a time in LDS, ENV_ROWS rows
+// of one value per member each,
+//     0-5 dx[c]   6-7 du[r]   8 one = 1.0   9 pen = 0.0      for a member that counts,
+//     0-5 0.0     6-7 0.0     8 one = 0.0   9 pen = +inf     for one that does not (selected, never multiplied: its NaN
+//                                                            stays in its lane),
+// and then turn the work round: lane L reduces ITEM L over the 64 members.  With v = (dx0..dx5, one) every sum of the
+// record is a sum of v_i v_j over the members — n = one.one, sum dx_i = dx_i.one, the moments dx_i.dx_j — 28 pairs per
+// sample, dealt as 14 tasks (a; b, c) = the pairs (a,b) and (a,c) that share row a: three LDS reads and two fused
+// multiply-adds per member, in member order 0..63 (the order is fixed, so are the bits; one.one and dx.one are exact).
+// ENV_S samples x 14 tasks occupy 56 lanes.  min / max: lane L = (sample L/16, quantity (L/2)%8, half L%2 of the members)
+// folds min(v + pen) and max(v - pen), the halves meet through one shuffle.  The item lanes read two members at a time
+// (ds_read_b128: 256 B per LDS cycle; the ds_read2_b64 the compiler makes of 8-byte reads runs at half that), so rows are
+// 16-byte aligned, ENV_LD = 66 doubles apart: lanes on different rows and one column meet on a bank only where their
+// rows are 16 apart.  Each tile's records go to `part[tile][t][44]`; k_envelope_fold folds the tiles of an optimum in tile order.
+constexpr int ENV_NREC = 44;    // AOC_ENV_NREC
+constexpr int ENV_S = 4;        // samples staged per reduction
+constexpr int ENV_ROWS = 10;
+constexpr int ENV_LD = TILE + 2;
+constexpr int ENV_NTASK = 14;
+static_assert(ENV_S * ENV_NTASK <= TILE && ENV_S * 16 == TILE, "one reduction occupies one wavefront");
+static_assert(ENS_BLK % ENV_S == 0, "a block of stage records is a whole number of envelope blocks");
+
+// index in the record of the sum over the members of v_i v_j, v = (dx0..dx5, one)
+__host__ __device__ constexpr int env_rec(int i, int j) {
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    return hi == 6 ? (lo == 6 ? 0 : 17 + lo) : 23 + lo * 6 - lo * (lo - 1) / 2 + (hi - lo);
+}
+// task k = (a, b, c), four bits each: the 28 pairs of the upper triangle of v v^T, two per task, sharing row a
+__host__ __device__ constexpr unsigned env_task(int k) {
+    constexpr unsigned t[ENV_NTASK] = {0x001, 0x023, 0x045, 0x112, 0x134, 0x156, 0x223, 0x245, 0x334, 0x356, 0x445, 0x556,
+                                       0x602, 0x646};
+    return t[k];
+}
+constexpr bool env_tasks_cover() {
+    bool seen[ENV_NREC] = {};
+    int n = 0;
+    for (int k = 0; k < ENV_NTASK; k++) {
+        const int a = env_task(k) >> 8, b = (env_task(k) >> 4) & 15, c = env_task(k) & 15;
+        for (int r : {env_rec(a, b), env_rec(a, c)}) {
+            if (r < 0 || r >= ENV_NREC || seen[r]) return false;
+            seen[r] = true;
+            n++;
+        }
+    }
+    return n == 28 && seen[0] && !seen[1] && !seen[16] && seen[17] && seen[43];
+}
+static_assert(env_tasks_cover(), "the 14 tasks are the 28 sums of the record, each once");
+
 // max over |v| with a NaN that sticks (fmax would drop it): for non-negative doubles the IEEE order is the order of
 // the bit patterns as unsigned integers, and every NaN lies above +inf there
 __device__ __forceinline__ void ens_absmax(unsigned long long& m, double v) {
@@ -35,13 +85,16 @@ __device__ __forceinline__ bool ens_finite6(const real x[6]) {
 
 // WRITE: x_reg / u_reg / dist_out (each may still be NULL) are written; NOISE: d_t drawn by mpc_noise_draw with the counter
 // (first + member, step + t, c / 2, 0); the stats-only, noise-free instance carries neither stores nor the generator.
-template <bool WRITE, bool NOISE, typename XO, bool DIAG>
+// ENV: also the per-tile envelope records part[tile][t][ENV_NREC] (above); every other output keeps its bits.
+template <bool WRITE, bool NOISE, typename XO, bool DIAG, bool ENV = false>
 __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_per_opt, const real* __restrict__ nominal,
                                                          const real* __restrict__ x0, MpcNoise nz, XO* __restrict__ x_reg,
                                                          real* __restrict__ u_reg, real* __restrict__ dist_out,
-                                                         real* __restrict__ stats, int* __restrict__ status) {
+                                                         real* __restrict__ stats, int* __restrict__ status,
+                                                         real* __restrict__ part = nullptr) {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(16))) real sh[2][ENS_BLK * ENS_REC];
+    __shared__ __attribute__((aligned(16))) real ev[ENV ? ENV_S * ENV_ROWS * ENV_LD : 2];
     // uniform constants in VGPRs (aoc_device.h pin_consts) where the SGPRs do not hold them: the diagonal weights (dense
     // ones are re-loaded from the kernel arguments inside the stage), and beside the generator's constants the model too
     KConst k = kc;
@@ -66,6 +119,70 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
 #pragma unroll
         for (int i = 0; i < ENS_PF; i++) sh[b & 1][i * TILE + lane] = pf[i];
         __syncthreads();   // one wavefront: orders the LDS writes before the broadcast reads, costs nothing
+    };
+    // envelope: what this lane reduces (fixed for the whole kernel) and where its results go
+    const bool in_B = tile * TILE + lane < k.B;   // the lanes that replicate member B-1 never count
+    const int e_s = lane / ENV_NTASK, e_k = lane - e_s * ENV_NTASK;            // sums: sample slot, task
+    const unsigned e_t = env_task(e_k);
+    const int e_a = e_t >> 8, e_b = (e_t >> 4) & 15, e_c = e_t & 15;
+    const int e_row = (e_s < ENV_S ? e_s : 0) * ENV_ROWS;
+    const real2v* __restrict__ pa = (const real2v*)&ev[ENV ? (e_row + (e_a == 6 ? 8 : e_a)) * ENV_LD : 0];
+    const real2v* __restrict__ pb = (const real2v*)&ev[ENV ? (e_row + (e_b == 6 ? 8 : e_b)) * ENV_LD : 0];
+    const real2v* __restrict__ pc = (const real2v*)&ev[ENV ? (e_row + (e_c == 6 ? 8 : e_c)) * ENV_LD : 0];
+    const int e_rb = env_rec(e_a, e_b), e_rc = env_rec(e_a, e_c);
+    const int m_s = lane >> 4, m_q = (lane >> 1) & 7, m_h = lane & 1;          // min / max: sample slot, quantity, half
+    const real2v* __restrict__ pv = (const real2v*)&ev[ENV ? (m_s * ENV_ROWS + m_q) * ENV_LD + m_h * (TILE / 2) : 0];
+    const real2v* __restrict__ pp = (const real2v*)&ev[ENV ? (m_s * ENV_ROWS + 9) * ENV_LD + m_h * (TILE / 2) : 0];
+    const int m_rmin = m_q < 6 ? 1 + m_q : 7 + m_q, m_rmax = m_q < 6 ? 7 + m_q : 9 + m_q;
+    // sample t of this member into slot t % ENV_S
+    auto env_put = [&](int t, const real dx[6], real du0, real du1, bool counts) {
+        real* __restrict__ row = &ev[(t & (ENV_S - 1)) * ENV_ROWS * ENV_LD + lane];
+#pragma unroll
+        for (int c = 0; c < 6; c++) row[c * ENV_LD] = counts ? dx[c] : R(0.0);
+        row[6 * ENV_LD] = counts ? du0 : R(0.0);
+        row[7 * ENV_LD] = counts ? du1 : R(0.0);
+        row[8 * ENV_LD] = counts ? R(1.0) : R(0.0);
+        row[9 * ENV_LD] = counts ? R(0.0) : (real)__builtin_inf();
+    };
+    // the samples tb .. tb + ns - 1 (slots 0 .. ns-1) over the 64 members of the tile
+    auto env_reduce = [&](int tb, int ns) {
+        __syncthreads();   // one wavefront: the rows are written
+        real s1 = R(0.0), s2 = R(0.0);
+#pragma nounroll   // sixteen members' loads in flight (96 VGPRs): more would not fit beside the state of the stage
+        for (int m0 = 0; m0 < TILE / 2; m0 += 8) {
+#pragma unroll
+            for (int m = 0; m < 8; m++) {   // members 2 (m0 + m) and 2 (m0 + m) + 1, in that order
+                const real2v a = pa[m0 + m], b = pb[m0 + m], c = pc[m0 + m];
+                s1 = __builtin_fma(a.y, b.y, __builtin_fma(a.x, b.x, s1));
+                s2 = __builtin_fma(a.y, c.y, __builtin_fma(a.x, c.x, s2));
+            }
+        }
+        real mn = (real)__builtin_inf(), mxv = -(real)__builtin_inf();
+#pragma nounroll
+        for (int m0 = 0; m0 < TILE / 4; m0 += 8) {
+#pragma unroll
+            for (int m = 0; m < 8; m++) {
+                const real2v v = pv[m0 + m], pen = pp[m0 + m];
+                mn = __builtin_fmin(__builtin_fmin(mn, v.x + pen.x), v.y + pen.y);
+                mxv = __builtin_fmax(__builtin_fmax(mxv, v.x - pen.x), v.y - pen.y);
+            }
+        }
+        mn = __builtin_fmin(mn, __shfl_xor(mn, 1));
+        mxv = __builtin_fmax(mxv, __shfl_xor(mxv, 1));
+        if (m_q >= 6 && tb + m_s == T - 1) {   // no input at the last sample: the empty set
+            mn = (real)__builtin_inf();
+            mxv = -(real)__builtin_inf();
+        }
+        real* __restrict__ po = part + ((size_t)tile * T + tb) * ENV_NREC;
+        if (lane < ENV_S * ENV_NTASK && e_s < ns) {
+            po[e_s * ENV_NREC + e_rb] = s1;
+            po[e_s * ENV_NREC + e_rc] = s2;
+        }
+        if (m_h == 0 && m_s < ns) {
+            po[m_s * ENV_NREC + m_rmin] = mn;
+            po[m_s * ENV_NREC + m_rmax] = mxv;
+        }
+        __syncthreads();   // the rows are read before the next samples overwrite them
     };
     unsigned long long mx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     real JJ = R(0.0);
@@ -104,6 +221,10 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
         for (int c = 0; c < 6; c++) ens_absmax(mx[c], d[c]);
         ens_absmax(mx[6], u0 - cur[6]);
         ens_absmax(mx[7], u1 - cur[7]);
+        if (ENV) {
+            env_put(t, d, u0 - cur[6], u1 - cur[7], in_B && first_bad > t);
+            if ((t & (ENV_S - 1)) == ENV_S - 1) env_reduce(t - (ENV_S - 1), ENV_S);
+        }
         JJ += stage_cost2<DIAG>(k, xs, u0, u1, cur, q, r);   // as k_traj_cost with ref = (x_opt, u_opt)
         // Everything that reads the record is above; the plant step below (three quarters of the stage) does not.  The
         // record of stage t+1 is read HERE from LDS — every lane the same address: a broadcast — into the registers this
@@ -148,6 +269,10 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
     const bool nonfin = !ens_finite6(xs);
     if (nonfin) flags |= AOC_ST_NAN;
     if ((nonfin || !(xs[2] > R(0.0))) && T - 1 < first_bad) first_bad = T - 1;
+    if (ENV) {
+        env_put(T - 1, dT, R(0.0), R(0.0), in_B && first_bad > T - 1);
+        env_reduce((T - 1) & ~(ENV_S - 1), ((T - 1) & (ENV_S - 1)) + 1);
+    }
     JJ += term_cost2<DIAG>(k, xs, cur, q);
     if (WRITE && x_reg) {
         st_stream(&u_reg[tix<2>(tile, T, T - 1, 0, lane)], R(0.0));
@@ -167,31 +292,74 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
     if (status && flags) status[tile * TILE + lane] |= flags;
 }
 
-#ifndef AOC_KERNELS_ONLY
-// Body of aoc_track_ensemble.  A template only so that the kernels it names are instantiated where it is called — from
-// the fp64 entry point — and not once more in the float32 namespace.
+// envelope[opt][t][q] from part[tile][t][q]: the tiles of an optimum folded in tile order, one thread per number (a sum for
+// q = 0 and q >= 17, a minimum for 1-6 and 13-14, a maximum for 7-12 and 15-16).  No atomics: the order is the tile order.
+// (A template like k_track_ensemble: instantiated by the fp64 launch function only.)
+constexpr int ENV_FOLD_THREADS = 256;
 template <typename = void>
-static int api_track_ensemble(const aoc_problem* p, int32_t n_opt, int32_t members_per_opt, const real* nominal,
-                              const real* x0_reg, const aoc_mpc_noise* noise, void* x_reg, real* u_reg, real* dist_out,
-                              real* stats, int32_t* status) {
-    if (!p) return einval("aoc_track_ensemble: aoc_problem is NULL");
-    if (!nominal) return einval("aoc_track_ensemble: nominal is NULL");
-    if (!x0_reg) return einval("aoc_track_ensemble: x0_reg is NULL");
-    if (!stats) return einval("aoc_track_ensemble: stats is NULL");
-    if (n_opt < 1) return einval("aoc_track_ensemble: n_opt = %d (need n_opt >= 1)", n_opt);
+__global__ __launch_bounds__(ENV_FOLD_THREADS) void k_envelope_fold(int n_opt, int T, int ntiles, int tiles_per_opt,
+                                                                    const real* __restrict__ part, real* __restrict__ envelope) {
+    const size_t per_opt = (size_t)T * ENV_NREC, idx = (size_t)blockIdx.x * ENV_FOLD_THREADS + threadIdx.x;
+    if (idx >= (size_t)n_opt * per_opt) return;
+    const int opt = (int)(idx / per_opt), q = (int)(idx % ENV_NREC);
+    const int first = opt * tiles_per_opt, last = first + tiles_per_opt < ntiles ? first + tiles_per_opt : ntiles;
+    const real* __restrict__ src = part + (size_t)first * per_opt + (idx - (size_t)opt * per_opt);
+    const int kind = (q == 0 || q >= 17) ? 0 : ((q <= 6 || q == 13 || q == 14) ? 1 : 2);
+    real acc = kind == 0 ? R(0.0) : (kind == 1 ? (real)__builtin_inf() : -(real)__builtin_inf());
+    int i = first;
+    for (; i + 16 <= last; i += 16) {   // sixteen loads in flight, folded in order
+        real v[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) v[j] = src[(size_t)j * per_opt];
+#pragma unroll
+        for (int j = 0; j < 16; j++) acc = kind == 0 ? acc + v[j] : (kind == 1 ? __builtin_fmin(acc, v[j]) : __builtin_fmax(acc, v[j]));
+        src += 16 * per_opt;
+    }
+    for (; i < last; i++, src += per_opt)
+        acc = kind == 0 ? acc + *src : (kind == 1 ? __builtin_fmin(acc, *src) : __builtin_fmax(acc, *src));
+    envelope[idx] = acc;
+}
+
+#ifndef AOC_KERNELS_ONLY
+// aoc_ensemble_envelope_scratch_bytes: part[ntiles][T][ENV_NREC]; 0 for a geometry the call refuses anyway
+static size_t ensemble_envelope_scratch_bytes(int32_t B, int32_t T, int32_t members_per_opt) {
+    if (B < 1 || T < 1 || members_per_opt < TILE || members_per_opt % TILE) return 0;
+    return (size_t)((B + TILE - 1) / TILE) * (size_t)T * ENV_NREC * sizeof(double);
+}
+
+// Body of aoc_track_ensemble and (env: with envelope, scratch, scratch_bytes) of aoc_track_ensemble_envelope, fn the name
+// of the entry point for the reasons.  A template only so that the kernels it names are instantiated where it is called
+// — from the fp64 entry points — and not once more in the float32 namespace.
+template <typename = void>
+static int api_track_ensemble(const char* fn, bool env, const aoc_problem* p, int32_t n_opt, int32_t members_per_opt,
+                              const real* nominal, const real* x0_reg, const aoc_mpc_noise* noise, void* x_reg, real* u_reg,
+                              real* dist_out, real* stats, int32_t* status, real* envelope, void* scratch,
+                              size_t scratch_bytes) {
+    if (!p) return einval("%s: aoc_problem is NULL", fn);
+    if (!nominal) return einval("%s: nominal is NULL", fn);
+    if (!x0_reg) return einval("%s: x0_reg is NULL", fn);
+    if (!stats) return einval("%s: stats is NULL", fn);
+    if (env && !envelope) return einval("%s: envelope is NULL", fn);
+    if (n_opt < 1) return einval("%s: n_opt = %d (need n_opt >= 1)", fn, n_opt);
     if (members_per_opt < TILE || members_per_opt % TILE)
-        return einval("aoc_track_ensemble: members_per_opt = %d is not a positive multiple of %d", members_per_opt, TILE);
-    if (p->T < 3) return einval("aoc_track_ensemble: T = %d (need T >= 3)", p->T);
+        return einval("%s: members_per_opt = %d is not a positive multiple of %d", fn, members_per_opt, TILE);
+    if (p->T < 3) return einval("%s: T = %d (need T >= 3)", fn, p->T);
     if ((long long)p->B <= (long long)(n_opt - 1) * members_per_opt || (long long)p->B > (long long)n_opt * members_per_opt)
-        return einval("aoc_track_ensemble: B = %d members do not fill n_opt = %d groups of members_per_opt = %d (need %lld < B <= %lld)",
+        return einval("%s: B = %d members do not fill n_opt = %d groups of members_per_opt = %d (need %lld < B <= %lld)", fn,
                       p->B, n_opt, members_per_opt, (long long)(n_opt - 1) * members_per_opt, (long long)n_opt * members_per_opt);
     if ((x_reg == nullptr) != (u_reg == nullptr))
-        return einval("aoc_track_ensemble: x_reg and u_reg go together (one of them is NULL)");
+        return einval("%s: x_reg and u_reg go together (one of them is NULL)", fn);
     if (p->x_out_f32 && x_reg && noise)
-        return einval("aoc_track_ensemble: float32 state storage (x_out_f32 = 1) cannot hold disturbed states: with noise "
-                      "x_reg must be fp64");
+        return einval("%s: float32 state storage (x_out_f32 = 1) cannot hold disturbed states: with noise "
+                      "x_reg must be fp64", fn);
     if (p->RRt[1] != p->RRt[2])
-        return einval("aoc_track_ensemble: aoc_problem.RRt is not symmetric (R01 = %g, R10 = %g)", p->RRt[1], p->RRt[2]);
+        return einval("%s: aoc_problem.RRt is not symmetric (R01 = %g, R10 = %g)", fn, p->RRt[1], p->RRt[2]);
+    if (env) {
+        const size_t need = ensemble_envelope_scratch_bytes(p->B, p->T, members_per_opt);
+        if (!scratch) return einval("%s: scratch is NULL (need %zu bytes, aoc_ensemble_envelope_scratch_bytes)", fn, need);
+        if (scratch_bytes < need)
+            return einval("%s: scratch_bytes = %zu, need %zu (aoc_ensemble_envelope_scratch_bytes)", fn, scratch_bytes, need);
+    }
     KConst k = make_const(p->model, p->QQt, p->RRt, p->QQT, p->B, p->T);
     MpcNoise nz;
     memset(&nz, 0, sizeof nz);
@@ -207,12 +375,29 @@ static int api_track_ensemble(const aoc_problem* p, int32_t n_opt, int32_t membe
 #define AOC_ENS_LAUNCH(W, N, XO, D)                                                                                     \
     hipLaunchKernelGGL((k_track_ensemble<W, N, XO, D>), dim3(k.ntiles), dim3(TILE), 0, st, k, tpo, nominal, x0_reg, nz, \
                        (XO*)x_reg, u_reg, dist_out, stats, status)
-    if (p->x_out_f32 && x_reg)   // (never with noise, see above)
-        AOC_DISPATCH_BOOL(k.diag, D, AOC_ENS_LAUNCH(true, false, float, D));
-    else
-        AOC_DISPATCH_BOOL(write, W, AOC_DISPATCH_BOOL(nz.on, N, AOC_DISPATCH_BOOL(k.diag, D, AOC_ENS_LAUNCH(W, N, double, D))));
+#define AOC_ENV_LAUNCH(W, N, XO, D)                                                                                      \
+    hipLaunchKernelGGL((k_track_ensemble<W, N, XO, D, true>), dim3(k.ntiles), dim3(TILE), 0, st, k, tpo, nominal, x0_reg, \
+                       nz, (XO*)x_reg, u_reg, dist_out, stats, status, (real*)scratch)
+#define AOC_ENS_DISPATCH(LAUNCH)                                                                                        \
+    do {                                                                                                                \
+        if (p->x_out_f32 && x_reg) /* (never with noise, see above) */                                                  \
+            AOC_DISPATCH_BOOL(k.diag, D, LAUNCH(true, false, float, D));                                                \
+        else                                                                                                            \
+            AOC_DISPATCH_BOOL(write, W, AOC_DISPATCH_BOOL(nz.on, N, AOC_DISPATCH_BOOL(k.diag, D, LAUNCH(W, N, double, D)))); \
+    } while (0)
+    if (!env) {
+        AOC_ENS_DISPATCH(AOC_ENS_LAUNCH);
+        return check_launch(fn);
+    }
+    AOC_ENS_DISPATCH(AOC_ENV_LAUNCH);
+    if (int rc = check_launch(fn)) return rc;
+    const size_t total = (size_t)n_opt * p->T * ENV_NREC;
+    hipLaunchKernelGGL(k_envelope_fold<>, dim3((unsigned)((total + ENV_FOLD_THREADS - 1) / ENV_FOLD_THREADS)),
+                       dim3(ENV_FOLD_THREADS), 0, st, n_opt, p->T, k.ntiles, tpo, (const real*)scratch, envelope);
+#undef AOC_ENS_DISPATCH
+#undef AOC_ENV_LAUNCH
 #undef AOC_ENS_LAUNCH
-    return check_launch("aoc_track_ensemble");
+    return check_launch(fn);
 }
 #endif  // AOC_KERNELS_ONLY
 

@@ -6,6 +6,11 @@ JSON line.
 
     python examples/run_tracking_ensemble.py [--data Data] [--members 65536] [--sigma 1e-3 1e-3 1e-2 1e-4 1e-3 1e-4]
                                              [--delta 0.3 0.3 0.5 0.05 0.1 0.05] [--seed 1] [--dt 1e-3]
+                                             [--envelope FILE.npz]
+
+--envelope FILE.npz: also reduce over the members at every sample on the device (the tube around the optimum) and save
+n (T,), min_dx / max_dx (6,T), min_du / max_du (2,T), mean_dx (6,T), cov_dx (6,6,T), raw (T,44); the JSON line then
+carries "envelope": the file, n at the last sample and the largest band width max_dx - min_dx per state.
 """
 import argparse
 import json
@@ -26,6 +31,7 @@ def main():
                     help="std of the perturbation of the initial state")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dt", type=float, default=1e-3)
+    ap.add_argument("--envelope", default=None, metavar="FILE.npz", help="save the per-sample envelope over the members")
     a = ap.parse_args()
     xx_opt = np.load(os.path.join(a.data, "xx_star.npy"))
     uu_opt = np.load(os.path.join(a.data, "uu_star.npy"))
@@ -33,11 +39,19 @@ def main():
     Q, R, QT = problems.tracking_weights()                           # lqr_tracking.py:324-328
     bp = batch.BatchProblem(Q, R, QT, np.zeros((6, T)), np.zeros((2, T)), a.dt)
     delta = np.random.default_rng(a.seed).normal(size=(a.members, 6)) * np.asarray(a.delta)
-    r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed)
+    r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, envelope=a.envelope is not None)
     sm = r["summary"][0]
     tolist = lambda d: {k: np.asarray(v).tolist() for k, v in d.items()}
-    print(json.dumps(dict(members=a.members, T=T, sigma=a.sigma, left_the_domain=sm["n_bad"],
-                          max_dx=tolist(sm["max_dx"]), final_dx=tolist(sm["final_dx"]), cost=tolist(sm["cost"]))))
+    line = dict(members=a.members, T=T, sigma=a.sigma, left_the_domain=sm["n_bad"],
+                max_dx=tolist(sm["max_dx"]), final_dx=tolist(sm["final_dx"]), cost=tolist(sm["cost"]))
+    if a.envelope is not None:
+        env = r["envelope"][0]
+        np.savez(a.envelope, **env)
+        some = env["n"] > 0                                          # an empty sample has the band +inf .. -inf
+        width = (env["max_dx"] - env["min_dx"])[:, some]
+        line["envelope"] = dict(file=a.envelope, n_last=int(env["n"][-1]),
+                                max_width=width.max(axis=1).tolist() if some.any() else None)
+    print(json.dumps(line))
 
 
 if __name__ == "__main__":

@@ -58,7 +58,9 @@ extern "C" {
  *   5: aoc_mpc_step takes aoc_mpc_noise (the disturbance drawn on the device) and disturbance_out; the horizon cut is
  *      decided once per aoc_newton_solve from the caller's batch (a trajectory's bits no longer depend on the generation or
  *      half it is solved in); aoc_tuning.fw_wpe1, hcut_chain6, bw_hcut_full, fw_duo, hcut_waves, hcut_pairs
- *      (still 5, an addition: aoc_track_ensemble — no struct, argument list or size query changed) */
+ *      (still 5, an addition: aoc_track_ensemble — no struct, argument list or size query changed)
+ *      (still 5, an addition: aoc_track_ensemble_envelope, aoc_ensemble_envelope_scratch_bytes — no struct, argument list
+ *      or size query of an existing entry changed) */
 #define AOC_ABI_VERSION 5
 
 #define AOC_TILE 64
@@ -525,6 +527,37 @@ int aoc_mpc_step(const aoc_problem *prob_track, const aoc_problem *prob_next, co
 int aoc_track_ensemble(const aoc_problem *prob, int32_t n_opt, int32_t members_per_opt, const double *nominal,
                        const double *x0_reg, const aoc_mpc_noise *noise, void *x_reg, double *u_reg, double *dist_out,
                        double *stats, int32_t *status);
+
+/* ---------------------------------------------------------------------------------------------
+ * The same ensemble, reduced OVER THE MEMBERS at every sample as well: the tube around each optimum.  Every argument that
+ * aoc_track_ensemble has means what it means there and is checked as there, and every output the two calls share (x_reg,
+ * u_reg, dist_out, stats, status) has the same bits from either.
+ * envelope: DEVICE, fp64, [n_opt][T][AOC_ENV_NREC], not NULL.  Record of optimum k at sample t over the members b of k that
+ *   COUNT at t: b < B (the lanes of the last tile that replicate member B-1 never count) and t < stats[15] of b (no sample
+ *   up to and including t had !(V > 0) or a non-finite component).  With dx = x_t - x_opt_t and du = u_t - u_opt_t:
+ *   0      n, the number of members that count (as a double)
+ *   1-6    min of dx[c]        7-12   max of dx[c]
+ *   13-14  min of du[r]        15-16  max of du[r]       (sample T-1 has no input: the empty-set values)
+ *   17-22  sum of dx[c]
+ *   23-43  sum of dx[i]*dx[j], i <= j, row by row of the upper triangle (00, 01, ..., 05, 11, ..., 55)
+ *   Empty set: min = +inf, max = -inf, sums = 0.  The sums are raw (not means, not centred): records of an ensemble cut into
+ *   several calls, shards or devices merge exactly in n / min / max and by addition in the sums.  A member that does not
+ *   count contributes nothing: its NaN reaches no sum, minimum or maximum.  du = K_t dx, so the input moments follow from
+ *   the record and the gains.
+ *   The order of every sum is fixed — members in index order within a tile (each product fused into its addition), tiles in
+ *   index order within an optimum, no atomics — so the same call gives the same bits every time, with or without
+ *   trajectories.
+ * scratch: DEVICE, caller-owned, at least aoc_ensemble_envelope_scratch_bytes(B, T, members_per_opt) bytes (one record per
+ *   tile and sample: 44 * 8 * T * ceil(B / 64)); NULL or too small is AOC_EINVAL with the reason.  Nothing is allocated.
+ * Two kernels on prob->stream: the ensemble kernel with the reduction over the 64 members of each tile, then the fold over
+ * the tiles of each optimum.
+ * --------------------------------------------------------------------------------------------- */
+#define AOC_ENV_NREC 44
+size_t aoc_ensemble_envelope_scratch_bytes(int32_t B, int32_t T, int32_t members_per_opt);
+int aoc_track_ensemble_envelope(const aoc_problem *prob, int32_t n_opt, int32_t members_per_opt, const double *nominal,
+                                const double *x0_reg, const aoc_mpc_noise *noise, void *x_reg, double *u_reg,
+                                double *dist_out, double *stats, int32_t *status, double *envelope, void *scratch,
+                                size_t scratch_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * float32 arithmetic (BASELINE.json configs[2]: "fp32 with tolerance sweep").

@@ -9,6 +9,13 @@
              the cheapest form of that path); its rollout kernel alone is k_track_rollout in the kernel trace
   B_stats    aoc_track_ensemble, statistics only         B_traj   ... writing x_reg (float32) and u_reg
   B_noise    ... statistics only, with the disturbance drawn on the device
+--envelope adds the per-sample envelope over the members (aoc_track_ensemble_envelope, 44 numbers per sample):
+  E_traj     the only way without it, part 1: aoc_track_ensemble writing x_reg and u_reg in fp64 (no dist_out)
+  E_reduce   ... part 2: the same 44 numbers per sample from those arrays with torch, on the tiled device arrays as they
+             lie (masked by first_bad; the moments as batched 6x64 by 64x6 fp64 products per tile and sample, summed over the
+             tiles — the fastest of four forms tried, EXPERIMENTS.md)
+  B_env      aoc_track_ensemble_envelope, statistics + envelope, no trajectories
+and reports E = E_traj + E_reduce, B_env / E and B_env / B_stats (the price of the reduction).
 The optimum is the g4 fixture's (T = 1000; --T cuts it), the members are seeded perturbations of its first sample.
 Profiler off: HIP events around at least --seconds of back-to-back launches per variant, after a warm-up of every variant;
 the variants take turns inside each of --repeats rounds, so that a drift of the machine hits all of them.  One JSON line:
@@ -33,8 +40,8 @@ DELTA_SCALE = np.array([0.3, 0.3, 0.5, 0.05, 0.1, 0.05])
 SIGMA = np.array([1e-3, 1e-3, 1e-2, 1e-4, 1e-3, 1e-4])
 
 
-def setup(B, T, g):
-    """Device buffers and the four launch closures for B members."""
+def setup(B, T, g, envelope=False):
+    """Device buffers and the launch closures for B members."""
     import torch
     from aircraftoptimalcontrol_amd import _lib, batch
     from aircraftoptimalcontrol_amd.batch import TILE, _ptr, alloc_tiled, check, lib, ntiles, pack, pack_vec
@@ -70,7 +77,60 @@ def setup(B, T, g):
                                        _ptr(xr) if traj else None, _ptr(ur) if traj else None, None, _ptr(stats),
                                        _ptr(status)), "aoc_track_ensemble")
 
-    return dict(A=run_A, B_stats=run_B, B_traj=lambda: run_B(traj=True), B_noise=lambda: run_B(noise=True))
+    runs = dict(A=run_A, B_stats=run_B, B_traj=lambda: run_B(traj=True), B_noise=lambda: run_B(noise=True))
+    if not envelope:
+        return runs
+    # E: trajectories in fp64 + a torch reduction on the tiled arrays [tile][t][c][lane]
+    xr64, ur64 = alloc_tiled(B, T, 6, dev), alloc_tiled(B, T, 2, dev)
+    pE = bp.c_problem(B)
+    xo_d, uo_d = nominal[0, :, 0:6], nominal[0, :, 6:8]   # (T,6), (T,2)
+    tt = torch.arange(T, device=dev)
+    inf = float("inf")
+    live = (torch.arange(nt * TILE, device=dev) < B).view(nt, 1, TILE)
+
+    def run_E_traj():
+        check(lib().aoc_track_ensemble(C.byref(pE), 1, nt * TILE, _ptr(nominal), _ptr(x0t), None, _ptr(xr64), _ptr(ur64), None,
+                                       _ptr(stats), _ptr(status)), "aoc_track_ensemble")
+
+    def run_E_reduce():
+        xv, uv = xr64.view(nt, T, 6, TILE), ur64.view(nt, T, 2, TILE)
+        counts = (tt.view(1, T, 1) < stats[:, 15, :].view(nt, 1, TILE)) & live       # (nt,T,64)
+        c4 = counts.unsqueeze(2)
+        dx, du = xv - xo_d.view(1, T, 6, 1), uv - uo_d.view(1, T, 2, 1)
+        rec = torch.empty((T, 44), dtype=torch.float64, device=dev)
+        rec[:, 0] = counts.sum(dim=(0, 2))
+        rec[:, 1:7] = torch.where(c4, dx, inf).amin(dim=(0, 3))
+        rec[:, 7:13] = torch.where(c4, dx, -inf).amax(dim=(0, 3))
+        rec[:, 13:15] = torch.where(c4, du, inf).amin(dim=(0, 3))
+        rec[:, 15:17] = torch.where(c4, du, -inf).amax(dim=(0, 3))
+        rec[T - 1, 13:15], rec[T - 1, 15:17] = inf, -inf
+        dz = torch.where(c4, dx, 0.0)
+        rec[:, 17:23] = dz.sum(dim=(0, 3))
+        mom = torch.zeros((T, 6, 6), dtype=torch.float64, device=dev)
+        for i in range(0, nt, 128):          # 6x64 by 64x6 per (tile, sample), then over the tiles: the fastest form tried
+            d = dz[i:i + 128]                # (one batched product over all members, K = B: 42 ms at 65 536; pair by pair: 12)
+            mom += torch.matmul(d, d.transpose(2, 3)).sum(dim=0)
+        iu = torch.triu_indices(6, 6, device=dev)
+        rec[:, 23:44] = mom[:, iu[0], iu[1]]
+        return rec
+
+    env = torch.empty((1, T, _lib.AOC_ENV_NREC), dtype=torch.float64, device=dev)
+    nbytes = int(lib().aoc_ensemble_envelope_scratch_bytes(B, T, nt * TILE))
+    scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+
+    def run_B_env():
+        check(lib().aoc_track_ensemble_envelope(C.byref(pB), 1, nt * TILE, _ptr(nominal), _ptr(x0t), None, None, None, None,
+                                                _ptr(stats), _ptr(status), _ptr(env), _ptr(scratch), nbytes),
+              "aoc_track_ensemble_envelope")
+
+    # the two ways agree before either is timed (n, min, max exactly; the sums to 1e-9 of their scale: a plausibility
+    # check of the yardstick, the tests hold the bound)
+    run_E_traj(); want = run_E_reduce(); run_B_env(); torch.cuda.synchronize()
+    got = env[0]
+    assert torch.equal(got[:, :17], want[:, :17]), "E and B_env disagree in n / min / max"
+    assert bool(((got[:, 17:] - want[:, 17:]).abs() <= 1e-9 * want[:, 17:].abs().max()).all()), "E and B_env disagree in the sums"
+    runs.update(E_traj=run_E_traj, E_reduce=run_E_reduce, B_env=run_B_env)
+    return runs
 
 
 def timed(fn, seconds):
@@ -103,7 +163,7 @@ def kernel_times(d):
     out = collections.OrderedDict()
     for name, t0, t1, grid in sorted(rows, key=lambda r: r[1]):
         name = name.split("(")[0].replace("void ", "").replace("aoc64::", "")
-        if name.startswith("k_track_"):
+        if name.startswith(("k_track_", "k_envelope_")):
             out.setdefault("%s grid=%s" % (name, grid), []).append(round((t1 - t0) / 1e6, 4))
     for k, v in out.items():
         print(json.dumps(dict(kernel=k, ms=v, median=float(np.median(v)), spread_rel=round((max(v) - min(v)) / float(np.median(v)), 4))))
@@ -118,6 +178,7 @@ def main():
     ap.add_argument("--valu", type=int, default=0, help="vector instructions per stage of the stats-only kernel (from the ISA)")
     ap.add_argument("--trace", action="store_true", help="three calls per variant and nothing else (under rocprofv3)")
     ap.add_argument("--kernel-times", default=None, metavar="DIR", help="summarise the kernel trace(s) under DIR (no GPU)")
+    ap.add_argument("--envelope", action="store_true", help="also time the per-sample envelope: E_traj + E_reduce against B_env")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.kernel_times:
@@ -130,7 +191,7 @@ def main():
     for B in a.members:
         rec = dict(members=B)
         try:
-            runs = setup(B, a.T, g)
+            runs = setup(B, a.T, g, a.envelope)
         except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
             rec["refused"] = "allocation refused: %s" % str(e).split("\n")[0]
             out["sizes"].append(rec)
@@ -153,6 +214,10 @@ def main():
             med = {k: float(np.median(v)) for k, v in ms.items()}
             rec["A_spread_rel"] = round((max(ms["A"]) - min(ms["A"])) / med["A"], 4)
             rec["B_over_A"] = {k: round(med[k] / med["A"], 4) for k in ms if k != "A"}
+            if a.envelope:
+                E = med["E_traj"] + med["E_reduce"]
+                rec["envelope"] = dict(E_ms=round(E, 4), B_env_over_E=round(med["B_env"] / E, 4),
+                                       B_env_over_B_stats=round(med["B_env"] / med["B_stats"], 4))
             stages = B * (a.T - 1)
             rec["member_stages_per_s"] = {k: round(stages / (med[k] * 1e-3), 0) for k in ms}
             if a.valu:
