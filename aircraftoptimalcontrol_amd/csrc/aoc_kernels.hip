@@ -257,6 +257,16 @@ constexpr int AOC_SPEC_MAX = 15;   // Armijo candidates that may ride along in t
 #undef AOC_REAL
 #undef R
 
+// aoc_pack / aoc_unpack and their _f32 forms: k_pack<ET> or k_unpack<ET> over (tiles, chunks of t)
+template <typename ST, typename DT>
+static int launch_layout(void (*kernel)(int, int, int, const ST*, DT*), const char* what, int32_t B, int32_t T, int32_t C,
+                         const ST* src, DT* dst, void* stream) {
+    if (!src || !dst || B < 1 || T < 1 || C < 1) return AOC_EINVAL;
+    dim3 grid(aoc_ntiles(B), T < 64 ? T : 64);
+    hipLaunchKernelGGL(kernel, grid, dim3(TILE), 0, (hipStream_t)stream, B, T, C, src, dst);
+    return check_launch(what);
+}
+
 extern "C" {
 
 const char* aoc_version(void) { return "aoc-hip 0.5 (gfx950)"; }
@@ -289,33 +299,17 @@ int32_t aoc_ntiles(int32_t B) { return (B + TILE - 1) / TILE; }
 size_t aoc_tiled_elems(int32_t B, int32_t T, int32_t C) { return (size_t)aoc_ntiles(B) * T * C * TILE; }
 
 int aoc_pack(int32_t B, int32_t T, int32_t C, const double* src, double* dst, void* stream) {
-    if (!src || !dst || B < 1 || T < 1 || C < 1) return AOC_EINVAL;
-    dim3 grid(aoc_ntiles(B), T < 64 ? T : 64);
-    hipLaunchKernelGGL(k_pack<double>, grid, dim3(TILE), 0, (hipStream_t)stream, B, T, C, src, dst);
-    return check_launch("k_pack");
+    return launch_layout(k_pack<double>, "k_pack", B, T, C, src, dst, stream);
 }
-
 int aoc_unpack(int32_t B, int32_t T, int32_t C, const double* src, double* dst, void* stream) {
-    if (!src || !dst || B < 1 || T < 1 || C < 1) return AOC_EINVAL;
-    dim3 grid(aoc_ntiles(B), T < 64 ? T : 64);
-    hipLaunchKernelGGL(k_unpack<double>, grid, dim3(TILE), 0, (hipStream_t)stream, B, T, C, src, dst);
-    return check_launch("k_unpack");
+    return launch_layout(k_unpack<double>, "k_unpack", B, T, C, src, dst, stream);
 }
-
 int aoc_pack_f32(int32_t B, int32_t T, int32_t C, const double* src, float* dst, void* stream) {
-    if (!src || !dst || B < 1 || T < 1 || C < 1) return AOC_EINVAL;
-    dim3 grid(aoc_ntiles(B), T < 64 ? T : 64);
-    hipLaunchKernelGGL(k_pack<float>, grid, dim3(TILE), 0, (hipStream_t)stream, B, T, C, src, dst);
-    return check_launch("k_pack");
+    return launch_layout(k_pack<float>, "k_pack", B, T, C, src, dst, stream);
 }
-
 int aoc_unpack_f32(int32_t B, int32_t T, int32_t C, const float* src, double* dst, void* stream) {
-    if (!src || !dst || B < 1 || T < 1 || C < 1) return AOC_EINVAL;
-    dim3 grid(aoc_ntiles(B), T < 64 ? T : 64);
-    hipLaunchKernelGGL(k_unpack<float>, grid, dim3(TILE), 0, (hipStream_t)stream, B, T, C, src, dst);
-    return check_launch("k_unpack");
+    return launch_layout(k_unpack<float>, "k_unpack", B, T, C, src, dst, stream);
 }
-
 
 int32_t aoc_spec_max(void) { return AOC_SPEC_MAX; }
 
@@ -348,11 +342,7 @@ int32_t aoc_default_nspec(int32_t B, int32_t armijo_maxiters) {
 
 size_t aoc_linesearch_scratch_bytes(int32_t B, int32_t T) {
     (void)T;
-    const size_t nt = (size_t)aoc_ntiles(B);
-    return align_up(nt * sizeof(unsigned long long), 16) + align_up((nt + 1) * sizeof(int), 16) +
-           align_up(nt * TILE * sizeof(int), 16) + align_up(sizeof(aoc64::LsState), 16) +
-           align_up(nt * TILE * aoc64::LS_WL_IPL * sizeof(int2), 16) + align_up(nt * TILE * sizeof(int), 16) +
-           align_up(2 * aoc64::LS_WL_ROUNDS * sizeof(int), 16);
+    return aoc64::ls_layout(aoc_ntiles(B), nullptr, nullptr);
 }
 
 
@@ -380,9 +370,11 @@ int aoc_backward(const aoc_problem* p, int32_t full_hessian, const void* x, cons
     return aoc64::api_backward(p, full_hessian, x, u, x0, Kt, lmbd0, status, scratch, scratch_bytes);
 }
 size_t aoc_backward_scratch_bytes(int32_t B, int32_t T) {
-    (void)T;
-    const int S = B >= 1 ? aoc64::hcut_segments(tuning().bw_hcut, aoc_ntiles(B)) : 0;
-    return S >= 2 ? aoc64::hcut_full_scratch_bytes(aoc_ntiles(B), S) : 0;   // (what a full-Hessian pass takes; Gauss-Newton: a part of it)
+    if (B < 1) return 0;
+    // the segments of a Gauss-Newton pass (a full-Hessian pass is cut in as many or not at all); what a full-Hessian pass
+    // takes (Gauss-Newton: a part of it)
+    const int S = aoc64::hcut_plan(aoc64::HCUT_GN, tuning().bw_hcut, aoc_ntiles(B), aoc_ntiles(B), T, nullptr, 0).S;
+    return S >= 2 ? aoc64::hcut_full_scratch_bytes(aoc_ntiles(B), S) : 0;
 }
 int aoc_gradient(const aoc_problem* p, const void* x, const double* u, const double* x0, double* du, double* slope,
                  int32_t* status) {

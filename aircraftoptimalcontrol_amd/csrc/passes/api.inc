@@ -112,6 +112,50 @@ static void hcut_launch_chain(int ntiles, int S, real* scratch, hipStream_t st) 
     if (np) hipLaunchKernelGGL(k_hcut_odd<AFFINE>, dim3(ntiles, np), dim3(TILE), 0, st, S, scratch);
 }
 
+// Is a pass cut, and how: the one place that decides it.  kind: the Gauss-Newton or full-Hessian backward pass of the Newton
+// iteration, or the tracking gains; knob: that pass's number of segments (aoc_tuning.bw_hcut / track_hcut); decide_ntiles: the
+// tile count the number of segments is chosen on, ntiles: the batch in flight.  S and bytes describe the cut the knob asks
+// for (aoc_backward_scratch_bytes sizes by them); `cut` says whether this pass takes it: at least two segments of at least
+// four stages, a grid of at most 1024 workgroups, scratch of `bytes`, fp64.
+enum HcutKind { HCUT_GN, HCUT_FULL, HCUT_TRACK };
+struct HcutPlan { int S; bool multiwave; size_t bytes; bool cut; };
+static HcutPlan hcut_plan(HcutKind kind, int knob, int decide_ntiles, int ntiles, int T, const void* scratch, size_t scratch_bytes) {
+    HcutPlan pl;
+    pl.S = hcut_segments(knob, decide_ntiles, kind == HCUT_FULL);
+    pl.multiwave = hcut_multiwave(tuning().hcut_waves, ntiles, pl.S);   // (scheduling only: bit-identical either way)
+    pl.bytes = pl.S < 2 ? 0 : kind == HCUT_FULL ? hcut_full_scratch_bytes(ntiles, pl.S) : hcut_scratch_bytes(ntiles, pl.S);
+    pl.cut = pl.S >= 2 && scratch && sizeof(real) == 8 && ntiles * pl.S <= 1024 && T - 1 >= 4 * pl.S && pl.bytes <= scratch_bytes;
+    return pl;
+}
+
+// The cut backward pass of the Newton iteration, Gauss-Newton or FULL Hessian: segment maps -> chain -> gains, on one or on
+// several wavefronts per (tile, segment).  FULL: the costate maps first, and at the end the sequential kernel for the tiles
+// the cut does not trust (round 5).
+template <bool FULL>
+static void hcut_launch_backward(const aoc_problem* p, const KConst& k, const HcutPlan& pl, const void* x, const real* u,
+                                 const real* x0, real* Kt, int32_t* status, void* scratch, hipStream_t st) {
+    const int S = pl.S;
+    HcutFull hf{nullptr, nullptr, nullptr, nullptr, 0};
+    if (FULL) {
+        hf = hcut_full_carve(scratch, k.ntiles, S);
+        hf.trust = tuning().bw_hcut_full >= 2;
+    }
+#define LAUNCH_HC(KERNEL, NY, NW, ...)                                                                                 \
+    AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,                                                       \
+        hipLaunchKernelGGL(KERNEL, dim3(k.ntiles, NY), dim3((NW) * TILE), 0, st, k, S, (const real*)p->ref, (const XT*)x, u, x0, __VA_ARGS__)))
+    if (FULL) LAUNCH_HC((k_bw_hcut_lam<D, RP, XT>), S, 1, hf);
+    if (pl.multiwave) LAUNCH_HC((k_bw_hcut_map3<D, RP, XT, FULL>), S, 3, Kt, (real*)scratch, status, hf);
+    else LAUNCH_HC((k_bw_hcut<D, RP, XT, false, FULL>), S, 1, Kt, (real*)scratch, status, hf);
+    hcut_launch_chain<true>(k.ntiles, S, (real*)scratch, st);
+    if (pl.multiwave) LAUNCH_HC((k_bw_hcut_gains2<D, RP, XT, FULL>), S - 1, 2, Kt, (real*)scratch, status, hf);
+    else LAUNCH_HC((k_bw_hcut<D, RP, XT, true, FULL>), S - 1, 1, Kt, (real*)scratch, status, hf);
+#undef LAUNCH_HC
+    if (FULL)
+        AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
+            hipLaunchKernelGGL((k_backward2<D, RP, true, true, XT>), dim3(k.ntiles), dim3(2 * TILE), 0, st, k, (const real*)p->ref,
+                               (const XT*)x, u, x0, Kt, (real*)nullptr, status, (const int*)hf.tile_flag, (const int*)hf.lane_flags)));
+}
+
 // hcut_ntiles: the tile count the horizon cut is decided on (0 = this batch's own).  aoc_newton_solve passes the tile count
 // of the CALLER's batch for every generation and half, so that a trajectory's bits do not depend on the batch it happens
 // to be solved in (re-packing and the two-stream split are scheduling only).
@@ -124,64 +168,16 @@ static int api_backward(const aoc_problem* p, int32_t full_hessian, const void* 
     KConst k = make_const(p);
     hipStream_t st = (hipStream_t)p->stream;
     const bool lam = full_hessian != 0 || lmbd0 != nullptr;
-    {   // Gauss-Newton iterations of batches that leave most SIMDs idle: the horizon in S segments (k_bw_hcut)
-        const int S = hcut_segments(tuning().bw_hcut, hcut_ntiles > 0 ? hcut_ntiles : k.ntiles, full_hessian != 0);
-        const bool mw = hcut_multiwave(tuning().hcut_waves, k.ntiles, S);   // (scheduling only: bit-identical either way)
-        if (!lam && S >= 2 && scratch && sizeof(real) == 8 && k.ntiles * S <= 1024 && p->T - 1 >= 4 * S &&
-            hcut_scratch_bytes(k.ntiles, S) <= scratch_bytes) {
-            const HcutFull hf0{nullptr, nullptr, nullptr, nullptr, 0};
-            if (mw) {
-                AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-                    hipLaunchKernelGGL((k_bw_hcut_map3<D, RP, XT, false>), dim3(k.ntiles, S), dim3(3 * TILE), 0, st, k, S, (const real*)p->ref,
-                                       (const XT*)x, u, x0, Kt, (real*)scratch, status, hf0)));
-            } else {
-                AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-                    hipLaunchKernelGGL((k_bw_hcut<D, RP, XT, false>), dim3(k.ntiles, S), dim3(TILE), 0, st, k, S, (const real*)p->ref,
-                                       (const XT*)x, u, x0, Kt, (real*)scratch, status)));
-            }
-            hcut_launch_chain<true>(k.ntiles, S, (real*)scratch, st);
-            if (mw) {
-                AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-                    hipLaunchKernelGGL((k_bw_hcut_gains2<D, RP, XT, false>), dim3(k.ntiles, S - 1), dim3(2 * TILE), 0, st, k, S, (const real*)p->ref,
-                                       (const XT*)x, u, x0, Kt, (real*)scratch, status, hf0)));
-            } else {
-                AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-                    hipLaunchKernelGGL((k_bw_hcut<D, RP, XT, true>), dim3(k.ntiles, S - 1), dim3(TILE), 0, st, k, S, (const real*)p->ref,
-                                       (const XT*)x, u, x0, Kt, (real*)scratch, status)));
-            }
-            return check_launch("k_bw_hcut");
-        }
-        // full-Hessian iterations (round 5): costate maps first, the sequential kernel for the tiles the cut does not trust
-        if (full_hessian && !lmbd0 && tuning().bw_hcut_full && S >= 2 && scratch && sizeof(real) == 8 && k.ntiles * S <= 1024 &&
-            p->T - 1 >= 4 * S && hcut_full_scratch_bytes(k.ntiles, S) <= scratch_bytes) {
-            HcutFull hf = hcut_full_carve(scratch, k.ntiles, S);
-            hf.trust = tuning().bw_hcut_full >= 2;
-            AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-                hipLaunchKernelGGL((k_bw_hcut_lam<D, RP, XT>), dim3(k.ntiles, S), dim3(TILE), 0, st, k, S, (const real*)p->ref,
-                                   (const XT*)x, u, x0, hf)));
-            if (mw) {
-                AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-                    hipLaunchKernelGGL((k_bw_hcut_map3<D, RP, XT, true>), dim3(k.ntiles, S), dim3(3 * TILE), 0, st, k, S, (const real*)p->ref,
-                                       (const XT*)x, u, x0, Kt, (real*)scratch, status, hf)));
-            } else {
-                AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-                    hipLaunchKernelGGL((k_bw_hcut<D, RP, XT, false, true>), dim3(k.ntiles, S), dim3(TILE), 0, st, k, S, (const real*)p->ref,
-                                       (const XT*)x, u, x0, Kt, (real*)scratch, status, hf)));
-            }
-            hcut_launch_chain<true>(k.ntiles, S, (real*)scratch, st);
-            if (mw) {
-                AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-                    hipLaunchKernelGGL((k_bw_hcut_gains2<D, RP, XT, true>), dim3(k.ntiles, S - 1), dim3(2 * TILE), 0, st, k, S, (const real*)p->ref,
-                                       (const XT*)x, u, x0, Kt, (real*)scratch, status, hf)));
-            } else {
-                AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-                    hipLaunchKernelGGL((k_bw_hcut<D, RP, XT, true, true>), dim3(k.ntiles, S - 1), dim3(TILE), 0, st, k, S, (const real*)p->ref,
-                                       (const XT*)x, u, x0, Kt, (real*)scratch, status, hf)));
-            }
-            AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-                hipLaunchKernelGGL((k_backward2<D, RP, true, true, XT>), dim3(k.ntiles), dim3(2 * TILE), 0, st, k, (const real*)p->ref,
-                                   (const XT*)x, u, x0, Kt, (real*)nullptr, status, (const int*)hf.tile_flag, (const int*)hf.lane_flags)));
-            return check_launch("k_bw_hcut (full Hessian)");
+    // batches that leave most SIMDs idle: the horizon in S segments (k_bw_hcut) — Gauss-Newton iterations, and full-Hessian
+    // ones (aoc_tuning.bw_hcut_full)
+    const bool cut_full = full_hessian && !lmbd0 && tuning().bw_hcut_full;
+    if (!lam || cut_full) {
+        const HcutPlan pl = hcut_plan(cut_full ? HCUT_FULL : HCUT_GN, tuning().bw_hcut, hcut_ntiles > 0 ? hcut_ntiles : k.ntiles,
+                                      k.ntiles, p->T, scratch, scratch_bytes);
+        if (pl.cut) {
+            if (cut_full) hcut_launch_backward<true>(p, k, pl, x, u, x0, Kt, status, scratch, st);
+            else hcut_launch_backward<false>(p, k, pl, x, u, x0, Kt, status, scratch, st);
+            return check_launch(cut_full ? "k_bw_hcut (full Hessian)" : "k_bw_hcut");
         }
     }
 #define LAUNCH_BW(F, L)                                                                                        \
@@ -310,16 +306,22 @@ static int api_forward(const aoc_problem* p, const aoc_params* prm, int32_t n_sp
     return check_launch("k_forward");
 }
 
-static void ls_carve(const aoc_problem* p, int ntiles, void* scratch, LsScratch& sc) {
+// The line-search scratch: one walk over its layout carves the pointers out of `scratch` (if given) and returns its size
+// (aoc_linesearch_scratch_bytes).  (LsState: the fp64 build's in either build, the larger of the two.)
+static size_t ls_layout(int ntiles, void* scratch, LsScratch* sc) {
     const size_t nt = (size_t)ntiles;
-    char* base = (char*)scratch;
-    sc.mask = (unsigned long long*)base;  base += align_up(nt * sizeof(unsigned long long), 16);
-    sc.prefix = (int*)base;               base += align_up((nt + 1) * sizeof(int), 16);
-    sc.first_ok = (int*)base;             base += align_up(nt * TILE * sizeof(int), 16);
-    sc.st = (LsState*)base;               base += align_up(sizeof(aoc64::LsState), 16);
-    sc.items = (int2*)base;               base += align_up(nt * TILE * LS_WL_IPL * sizeof(int2), 16);
-    sc.next_r = (int*)base;               base += align_up(nt * TILE * sizeof(int), 16);
-    sc.wl_count = (int*)base;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* q = scratch ? (char*)scratch + off : nullptr; off += align_up(bytes, 16); return q; };
+    LsScratch s;
+    s.mask = (unsigned long long*)take(nt * sizeof(unsigned long long));
+    s.prefix = (int*)take((nt + 1) * sizeof(int));
+    s.first_ok = (int*)take(nt * TILE * sizeof(int));
+    s.st = (LsState*)take(sizeof(aoc64::LsState));
+    s.items = (int2*)take(nt * TILE * LS_WL_IPL * sizeof(int2));
+    s.next_r = (int*)take(nt * TILE * sizeof(int));
+    s.wl_count = (int*)take(2 * LS_WL_ROUNDS * sizeof(int));
+    if (sc) *sc = s;
+    return off;
 }
 
 // work-list search (k_ls_init_wl ...) or round-based search (k_ls_init ...): by batch size unless aoc_tuning says otherwise
@@ -345,7 +347,7 @@ static int api_ls_search(const aoc_problem* p, const aoc_params* prm, int32_t n_
     KConst k = make_const(p);
     hipStream_t st = (hipStream_t)p->stream;
     LsScratch sc;
-    ls_carve(p, k.ntiles, scratch, sc);
+    ls_layout(k.ntiles, scratch, &sc);
     const aoc_tuning& tn = tuning();
     if (ls_use_worklist(k.ntiles)) {
         // work-list search: two rounds for armijo_maxiters <= n_spec + LS_WL_IPL * cpl (one more per further
@@ -446,7 +448,7 @@ static int api_ls_update(const aoc_problem* p, const aoc_params* prm, const real
     KConst k = make_const(p);
     hipStream_t st = (hipStream_t)p->stream;
     LsScratch sc;
-    ls_carve(p, k.ntiles, scratch, sc);
+    ls_layout(k.ntiles, scratch, &sc);
     if (k.ntiles <= tuning().split_tiles && p->T >= 3) {   // small batches: state chain and cost on two wavefronts
         // candidates the forward pass stored (aoc_forward with `cand`): the update of most tiles is then a copy
         const CandBuf cb = cand_carve(J_trial ? cand : nullptr, p->B, p->T, n_spec);
@@ -485,11 +487,11 @@ static int api_lqr_tracking(const aoc_problem* p, const void* x_opt, const real*
     KConst k = make_const(p);
     hipStream_t st = (hipStream_t)p->stream;
     const int split_tiles = tuning().split_tiles;
-    const int S = hcut_segments(tuning().track_hcut, k.ntiles);
-    if (S >= 2 && scratch && k.ntiles * S <= 1024 && p->T - 1 >= 4 * S && hcut_scratch_bytes(k.ntiles, S) <= scratch_bytes) {
+    const HcutPlan pl = hcut_plan(HCUT_TRACK, tuning().track_hcut, k.ntiles, k.ntiles, p->T, scratch, scratch_bytes);
+    if (pl.cut) {
         // the horizon in S segments (see k_track_hcut_map): for batches that leave most SIMDs idle
-        const bool mw = hcut_multiwave(tuning().hcut_waves, k.ntiles, S);   // every wavefront of the segment kernels still on a SIMD of its own
-        if (mw) {
+        const int S = pl.S;
+        if (pl.multiwave) {   // every wavefront of the segment kernels still on a SIMD of its own
             AOC_DISPATCH_BOOL(k.diag, D, AOC_DISPATCH_XT(p->x_in_f32, XT,
                 hipLaunchKernelGGL((k_track_hcut_map3<D, XT>), dim3(k.ntiles, S), dim3(3 * TILE), 0, st, k, S, (const XT*)x_opt, u_opt,
                                    x_opt0, Kgain, (real*)scratch, status)));
@@ -499,7 +501,7 @@ static int api_lqr_tracking(const aoc_problem* p, const void* x_opt, const real*
                                    x_opt0, Kgain, (real*)scratch, status)));
         }
         hcut_launch_chain<false>(k.ntiles, S, (real*)scratch, st);
-        if (mw) {
+        if (pl.multiwave) {
             AOC_DISPATCH_BOOL(k.diag, D, AOC_DISPATCH_XT(p->x_in_f32, XT,
                 hipLaunchKernelGGL((k_track_hcut_gains2<D, XT>), dim3(k.ntiles, S - 1), dim3(2 * TILE), 0, st, k, S, (const XT*)x_opt, u_opt,
                                    x_opt0, Kgain, (const real*)scratch, status)));

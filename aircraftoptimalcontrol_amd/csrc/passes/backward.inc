@@ -84,16 +84,22 @@ __device__ __forceinline__ void bw_produce(const KConst& k, const real* __restri
     }
 }
 
-template <bool FULL, typename Emit>
-__device__ __forceinline__ StageFlags bw_consume(const KConst& k, const BwIn& in, real P[21], real p[6],
-                                                 const real Qb[21], Emit emit) {
-    real Qs[21];
+// the stage's Q: the weights Qb, with FULL plus the Hessian terms fxx . lambda
+template <bool FULL>
+__device__ __forceinline__ void bw_stage_q(const BwIn& in, const real Qb[21], real Qs[21]) {
 #pragma unroll
     for (int e = 0; e < 21; e++) Qs[e] = Qb[e];
     if (FULL) {
         Qs[sidx(2, 2)] += in.dq[0]; Qs[sidx(2, 3)] += in.dq[1]; Qs[sidx(2, 5)] += in.dq[2];
         Qs[sidx(3, 3)] += in.dq[3]; Qs[sidx(3, 5)] += in.dq[4]; Qs[sidx(5, 5)] += in.dq[5];
     }
+}
+
+template <bool FULL, typename Emit>
+__device__ __forceinline__ StageFlags bw_consume(const KConst& k, const BwIn& in, real P[21], real p[6],
+                                                 const real Qb[21], Emit emit) {
+    real Qs[21];
+    bw_stage_q<FULL>(in, Qb, Qs);
     return lqr_stage(k, in.l, P, p, Qs, in.s02, in.s03, in.s05, in.hq, in.hr, emit);
 }
 
@@ -102,12 +108,7 @@ template <bool FULL, int COLS, bool AFFINE, typename Emit>
 __device__ __forceinline__ StageFlags bw_consume_part(const KConst& k, const BwIn& in, const real P[21], real p[6],
                                                       const real Qb[21], real Pn[21], Emit emit) {
     real Qs[21];
-#pragma unroll
-    for (int e = 0; e < 21; e++) Qs[e] = Qb[e];
-    if (FULL) {
-        Qs[sidx(2, 2)] += in.dq[0]; Qs[sidx(2, 3)] += in.dq[1]; Qs[sidx(2, 5)] += in.dq[2];
-        Qs[sidx(3, 3)] += in.dq[3]; Qs[sidx(3, 5)] += in.dq[4]; Qs[sidx(5, 5)] += in.dq[5];
-    }
+    bw_stage_q<FULL>(in, Qb, Qs);
     return lqr_stage_part<COLS, AFFINE>(k, in.l, P, p, Qs, in.s02, in.s03, in.s05, in.hq, in.hr, Pn, emit);
 }
 

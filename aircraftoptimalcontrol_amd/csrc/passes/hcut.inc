@@ -13,12 +13,88 @@
 //   k_track_hcut_chain  grid (tiles): the value function handed down from segment to segment through the maps
 //   k_track_hcut_gains  grid (tiles, S-1): every segment's own recursion and gains from its end value
 // Not bit-identical to the sequential kernels (gains agree to ~1e-13 of their scale, tools/probes/horizon_cut_numpy.py).
-// scratch per tile: S maps of HC_MAP doubles per lane + S boundary value functions of HC_BND (hcut_scratch_bytes).
+// Scratch (HcutScratch below is its one description): S maps per tile, then S boundary value functions per tile, then the
+// S / 2 composed maps per tile of k_hcut_pair; a map is HC_MAP planes of TILE values, a boundary HC_BND.
 // ---------------------------------------------------------------------------------------------
-constexpr int HC_MAP = 21 + 36 + 21 + 12;   // H (sym), Phi (row-major), Gam (sym); eta, beta (Newton backward pass only)
-constexpr int HC_BND = 21 + 6;               // P (sym), p
-// (+ the S / 2 composed maps per tile of k_hcut_pair behind them)
+// the planes of a map: H (sym), Phi (row-major), Gam (sym); eta, beta (Newton backward pass only) ...
+constexpr int HC_H = 0, HC_PHI = HC_H + 21, HC_GAM = HC_PHI + 36, HC_ETA = HC_GAM + 21, HC_BETA = HC_ETA + 6, HC_MAP = HC_BETA + 6;
+// ... and of a boundary value function: P (sym), p
+constexpr int HC_BP = 0, HC_Bp = HC_BP + 21, HC_BND = HC_Bp + 6;
+// The cut's scratch as the kernels see it: no kernel forms an address in it by itself.  (A map may also sit in LDS,
+// k_hcut_chain6: the plane constants and hc_load / hc_store serve both.)
+struct HcutScratch {
+    real* base;
+    int ntiles, S;
+    __device__ __forceinline__ HcutScratch(real* scratch, int ntiles_, int S_) : base(scratch), ntiles(ntiles_), S(S_) {}
+    // (the gains kernels are handed the scratch read-only)
+    __device__ __forceinline__ HcutScratch(const real* scratch, int ntiles_, int S_) : HcutScratch(const_cast<real*>(scratch), ntiles_, S_) {}
+    __device__ __forceinline__ real* map(int tile, int seg) const { return base + ((size_t)tile * S + seg) * HC_MAP * TILE; }
+    __device__ __forceinline__ real* bnd(int tile, int seg) const {
+        return base + (size_t)ntiles * S * HC_MAP * TILE + ((size_t)tile * S + seg) * HC_BND * TILE;
+    }
+    // composed map k of a tile (k_hcut_pair), behind the boundaries
+    __device__ __forceinline__ real* comp(int tile, int k) const {
+        return base + (size_t)ntiles * S * (HC_MAP + HC_BND) * TILE + ((size_t)tile * (S / 2) + k) * HC_MAP * TILE;
+    }
+};
 static size_t hcut_scratch_bytes(int ntiles, int S) { return (size_t)ntiles * (S * (HC_MAP + HC_BND) + (S / 2) * HC_MAP) * TILE * sizeof(real); }
+// N planes from `plane` on, of a map or a boundary m, to and from registers
+template <int N>
+__device__ __forceinline__ void hc_load(const real* __restrict__ m, int plane, int lane, real* v) {
+#pragma unroll
+    for (int e = 0; e < N; e++) v[e] = m[(size_t)(plane + e) * TILE + lane];
+}
+template <int N>
+__device__ __forceinline__ void hc_store(real* __restrict__ m, int plane, int lane, const real* v) {
+#pragma unroll
+    for (int e = 0; e < N; e++) m[(size_t)(plane + e) * TILE + lane] = v[e];
+}
+// the value function (P, p) of a boundary b (without AFFINE — tracking — p = 0 and is not stored)
+template <bool AFFINE>
+__device__ __forceinline__ void hc_load_value(const real* __restrict__ b, int lane, real P[21], real p[6]) {
+    hc_load<21>(b, HC_BP, lane, P);
+#pragma unroll
+    for (int e = 0; e < 6; e++) p[e] = AFFINE ? b[(size_t)(HC_Bp + e) * TILE + lane] : R(0.0);
+}
+template <bool AFFINE>
+__device__ __forceinline__ void hc_store_value(real* __restrict__ b, int lane, const real P[21], const real p[6]) {
+    hc_store<21>(b, HC_BP, lane, P);
+    if (AFFINE) hc_store<6>(b, HC_Bp, lane, p);
+}
+// a map in its two halves (see hcut_stage_h / hcut_stage_phi below; eta, beta: nullptr without the affine terms): the
+// identity map H = Gam = 0, Phi = I, eta = beta = 0, and the store of a finished one
+__device__ __forceinline__ void hc_init_h(real H[21], real* eta) {
+#pragma unroll
+    for (int e = 0; e < 21; e++) H[e] = R(0.0);
+    if (eta) {
+#pragma unroll
+        for (int e = 0; e < 6; e++) eta[e] = R(0.0);
+    }
+}
+__device__ __forceinline__ void hc_init_phi(real Phi[36], real Gam[21], real* beta) {
+#pragma unroll
+    for (int e = 0; e < 21; e++) Gam[e] = R(0.0);
+#pragma unroll
+    for (int e = 0; e < 36; e++) Phi[e] = (e % 7 == 0) ? R(1.0) : R(0.0);
+    if (beta) {
+#pragma unroll
+        for (int e = 0; e < 6; e++) beta[e] = R(0.0);
+    }
+}
+__device__ __forceinline__ void hc_store_h(real* __restrict__ m, int lane, const real H[21], const real* eta) {
+    hc_store<21>(m, HC_H, lane, H);
+    if (eta) hc_store<6>(m, HC_ETA, lane, eta);
+}
+__device__ __forceinline__ void hc_store_phi(real* __restrict__ m, int lane, const real Phi[36], const real Gam[21], const real* beta) {
+    hc_store<36>(m, HC_PHI, lane, Phi);
+    hc_store<21>(m, HC_GAM, lane, Gam);
+    if (beta) hc_store<6>(m, HC_BETA, lane, beta);
+}
+// FULL: is the iterate of this stage not finite?  (a trajectory that diverged earlier: nothing to protect)
+__device__ __forceinline__ bool hc_bad_input(const real xs[6], real u0, real u1) {
+    const real chk = (u0 + u1) + ((xs[0] + xs[1]) + (xs[2] + xs[3]) + (xs[4] + xs[5]));
+    return !(chk - chk == R(0.0));
+}
 // segment j: stages [cut(j), cut(j+1)).  The last segment only runs the plain recursion, cheaper per stage than a map, so it
 // is made AOC_HC_LAST10 tenths of a regular segment long.  Measured (MPC step of 16 tiles): with one wavefront per segment
 // (~880 instructions a stage against ~1140) flat from 1.2 to 1.4, with the stage on three / two wavefronts (longest part
@@ -187,6 +263,37 @@ __device__ __forceinline__ void hcut_stage(const KConst& k, const Lin& l, real H
     hcut_stage_phi<AFFINE>(k, m, Phi, Gam, beta);
 }
 
+// the plain recursion from (P, p = 0) over the stages t_hi-1 .. t_lo of a tile on ONE wavefront, gains stored: the last segment of
+// k_track_hcut_map and every segment of k_track_hcut_gains (hcut_track_recursion below is its LDS-fed counterpart)
+template <typename XT>
+__device__ __forceinline__ int hcut_track_segment(const KConst& k, const XT* __restrict__ x, const real* __restrict__ u,
+                                                  const real* __restrict__ x_opt0, int tile, int lane, int t_lo, int t_hi,
+                                                  real P[21], real* __restrict__ Kout) {
+    const int T = k.T;
+    real p[6], Qb[21], xs[6];
+    int flags = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) p[i] = R(0.0);
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = i; j < 6; j++) Qb[sidx(i, j)] = k.Q[i * 6 + j];
+    StageIn<XT> cur, nxt;
+    real x0r[6];
+    stage_x0(x_opt0, tile, lane, t_lo, x0r);
+    stage_fetch<false>(x, u, tile, T, t_hi - 1, lane, cur);
+    for (int t = t_hi - 1; t >= t_lo; t--) {
+        stage_fetch<false>(x, u, tile, T, t > t_lo ? t - 1 : t, lane, nxt);
+        stage_state(cur, x0r, t, xs);
+        const SC s = trig(xs[3], xs[5]);
+        Lin l = linearise(k, xs, cur.u0, s);
+        track_lin_fields(l, [](int, real& v) { bw_opaque(v); });   // the cut of k_track_hcut_map3 / _gains2: same roundings
+        flags |= track_gain_stage(k, l, P, p, Qb, Kout, tile, T, t, lane);
+        cur = nxt;
+    }
+    return flags;
+}
+
 template <bool DIAG, typename XT>
 __global__ __launch_bounds__(TILE) void k_track_hcut_map(KConst k, int S, const XT* __restrict__ x,
                                                          const real* __restrict__ u, const real* __restrict__ x_opt0,
@@ -194,55 +301,28 @@ __global__ __launch_bounds__(TILE) void k_track_hcut_map(KConst k, int S, const 
                                                          int* __restrict__ status) {
     const int tile = blockIdx.x, seg = blockIdx.y, lane = threadIdx.x, T = k.T;
     const int t_lo = hcut_cut(T, S, seg), t_hi = hcut_cut(T, S, seg + 1);   // stages t_hi-1 .. t_lo
-    real* maps = scratch + ((size_t)tile * S + seg) * HC_MAP * TILE;
-    real* bnd = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + ((size_t)tile * S + seg) * HC_BND * TILE;
-    real Qb[21], xs[6];
+    const HcutScratch hs(scratch, gridDim.x, S);
+    real* const maps = hs.map(tile, seg);
+    real* const bnd = hs.bnd(tile, seg);
     int flags = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = i; j < 6; j++) Qb[sidx(i, j)] = k.Q[i * 6 + j];
     if (seg == S - 1) {   // the last segment: the plain recursion from Q_T, its gains are final; P at its first stage out
-        real P[21], p[6];
+        real P[21];
 #pragma unroll
-        for (int i = 0; i < 6; i++) {
-            p[i] = R(0.0);
+        for (int i = 0; i < 6; i++)
 #pragma unroll
             for (int j = i; j < 6; j++) P[sidx(i, j)] = k.QT[i * 6 + j];
-        }
-        StageIn<XT> cur, nxt;
-        real x0r[6];
-        stage_x0(x_opt0, tile, lane, t_lo, x0r);
-        stage_fetch<false>(x, u, tile, T, t_hi - 1, lane, cur);
-        for (int t = t_hi - 1; t >= t_lo; t--) {
-            stage_fetch<false>(x, u, tile, T, t > t_lo ? t - 1 : t, lane, nxt);
-            stage_state(cur, x0r, t, xs);
-            const SC s = trig(xs[3], xs[5]);
-            Lin l = linearise(k, xs, cur.u0, s);
-            track_lin_fields(l, [](int, real& v) { bw_opaque(v); });   // the cut of k_track_hcut_map3: same roundings
-            real zz = R(0.0);
-            bw_opaque(zz);
-            const real z6[6] = {zz, zz, zz, zz, zz, zz}, z2[2] = {zz, zz};
-            const StageFlags fl = lqr_stage(k, l, P, p, Qb, zz, zz, zz, z6, z2, [&](int c, real a, real b) {
-                if (c >= 1) {
-                    Kout[tix<12>(tile, T, t, c - 1, lane)] = a;
-                    Kout[tix<12>(tile, T, t, 5 + c, lane)] = b;
-                }
-            });
-            if (fl.singular) flags |= AOC_ST_SINGULAR;
-            if (fl.regularised) flags |= AOC_ST_REGULARISED;
-            cur = nxt;
-        }
-#pragma unroll
-        for (int e = 0; e < 21; e++) bnd[(size_t)e * TILE + lane] = P[e];
+        flags = hcut_track_segment(k, x, u, x_opt0, tile, lane, t_lo, t_hi, P, Kout);
+        hc_store<21>(bnd, HC_BP, lane, P);
 #pragma unroll
         for (int j = 0; j < 12; j++) Kout[tix<12>(tile, T, T - 1, j, lane)] = R(0.0);  // KK[:,:,T-1] stays 0 (:700)
     } else {
-        real H[21], Phi[36], Gam[21];
+        real H[21], Phi[36], Gam[21], Qb[21], xs[6];
 #pragma unroll
-        for (int e = 0; e < 21; e++) { H[e] = R(0.0); Gam[e] = R(0.0); }
+        for (int i = 0; i < 6; i++)
 #pragma unroll
-        for (int e = 0; e < 36; e++) Phi[e] = (e % 7 == 0) ? R(1.0) : R(0.0);
+            for (int j = i; j < 6; j++) Qb[sidx(i, j)] = k.Q[i * 6 + j];
+        hc_init_h(H, nullptr);
+        hc_init_phi(Phi, Gam, nullptr);
         StageFlags fl{false, false};
         StageIn<XT> cur, nxt;
         real x0r[6];
@@ -258,12 +338,8 @@ __global__ __launch_bounds__(TILE) void k_track_hcut_map(KConst k, int S, const 
             cur = nxt;
         }
         if (fl.singular) flags |= AOC_ST_SINGULAR;
-#pragma unroll
-        for (int e = 0; e < 21; e++) maps[(size_t)e * TILE + lane] = H[e];
-#pragma unroll
-        for (int e = 0; e < 36; e++) maps[(size_t)(21 + e) * TILE + lane] = Phi[e];
-#pragma unroll
-        for (int e = 0; e < 21; e++) maps[(size_t)(57 + e) * TILE + lane] = Gam[e];
+        hc_store_h(maps, lane, H, nullptr);
+        hc_store_phi(maps, lane, Phi, Gam, nullptr);
     }
     if (status && flags) atomicOr(&status[tile * TILE + lane], flags);
 }
@@ -323,7 +399,7 @@ __device__ __forceinline__ void hc_solve6n(real X[6][6], real F[6][NR]) {
 __device__ __forceinline__ void hc_solve6(real X[6][6], real F[6][6]) { hc_solve6n<6>(X, F); }
 
 // one hop: the value function (P, p) at the END of a segment -> at its first stage, through the segment's map m
-// (H at 0, Phi at 21, Gam at 57, eta at 78, beta at 84; HC_MAP planes of TILE doubles)
+// (planes HC_H .. HC_BETA of TILE doubles, in the scratch or in LDS)
 template <bool AFFINE>
 __device__ __forceinline__ void hcut_hop(const real* __restrict__ m, int lane, real P[21], real p[6]) {
     real X[6][6], F[6][6];
@@ -334,9 +410,9 @@ __device__ __forceinline__ void hcut_hop(const real* __restrict__ m, int lane, r
         for (int j = 0; j < 6; j++) {
             real a = i == j ? R(1.0) : R(0.0);
 #pragma unroll
-            for (int q = 0; q < 6; q++) a += m[(size_t)(57 + (i <= q ? sidx(i, q) : sidx(q, i))) * TILE + lane] * hc_sym(P, q, j);
+            for (int q = 0; q < 6; q++) a += m[(size_t)(HC_GAM + (i <= q ? sidx(i, q) : sidx(q, i))) * TILE + lane] * hc_sym(P, q, j);
             X[i][j] = a;
-            F[i][j] = m[(size_t)(21 + i * 6 + j) * TILE + lane];
+            F[i][j] = m[(size_t)(HC_PHI + i * 6 + j) * TILE + lane];
         }
     hc_solve6(X, F);                       // F = (I + Gam P)^-1 Phi
     real Z[6][6];                          // Z = P F
@@ -355,12 +431,12 @@ __device__ __forceinline__ void hcut_hop(const real* __restrict__ m, int lane, r
         for (int i = 0; i < 6; i++) {
             real a = p[i];
 #pragma unroll
-            for (int q = 0; q < 6; q++) a += hc_sym(P, i, q) * m[(size_t)(84 + q) * TILE + lane];
+            for (int q = 0; q < 6; q++) a += hc_sym(P, i, q) * m[(size_t)(HC_BETA + q) * TILE + lane];
             v[i] = a;
         }
 #pragma unroll
         for (int j = 0; j < 6; j++) {
-            real a = m[(size_t)(78 + j) * TILE + lane];
+            real a = m[(size_t)(HC_ETA + j) * TILE + lane];
 #pragma unroll
             for (int q = 0; q < 6; q++) a += F[q][j] * v[q];
             p[j] = a;
@@ -371,9 +447,9 @@ __device__ __forceinline__ void hcut_hop(const real* __restrict__ m, int lane, r
     for (int i = 0; i < 6; i++)
 #pragma unroll
         for (int j = i; j < 6; j++) {
-            real a = m[(size_t)sidx(i, j) * TILE + lane];
+            real a = m[(size_t)(HC_H + sidx(i, j)) * TILE + lane];
 #pragma unroll
-            for (int q = 0; q < 6; q++) a += m[(size_t)(21 + q * 6 + i) * TILE + lane] * Z[q][j];
+            for (int q = 0; q < 6; q++) a += m[(size_t)(HC_PHI + q * 6 + i) * TILE + lane] * Z[q][j];
             P[sidx(i, j)] = a;
         }
 }
@@ -394,22 +470,20 @@ __device__ __forceinline__ void hcut_hop(const real* __restrict__ m, int lane, r
 // of segments (by default for cuts in at least 12 segments: hcut_launch_chain), never by the batch in flight.
 // Composed maps live behind the boundaries in the scratch (hcut_scratch_bytes).
 __host__ __device__ inline int hcut_npairs(int S) { return S >= 4 ? (S - 2) / 2 : 0; }
-__device__ __forceinline__ real* hcut_comp(real* scratch, int ntiles, int S, int tile, int k) {
-    return scratch + (size_t)ntiles * S * (HC_MAP + HC_BND) * TILE + ((size_t)tile * (S / 2) + k) * HC_MAP * TILE;
-}
 
 template <bool AFFINE>
 __global__ __launch_bounds__(2 * TILE) void k_hcut_pair(int S, real* __restrict__ scratch) {
     const int tile = blockIdx.x, k = blockIdx.y, lane = threadIdx.x & (TILE - 1), wv = threadIdx.x >> 6;
     const int j = S - 2 - 2 * k;                                             // maps j - 1 (earlier: 1) and j (later: 2)
-    const real* __restrict__ m1 = scratch + ((size_t)tile * S + (j - 1)) * HC_MAP * TILE + lane;
-    const real* __restrict__ m2 = scratch + ((size_t)tile * S + j) * HC_MAP * TILE + lane;
-    real* __restrict__ mc = hcut_comp(scratch, gridDim.x, S, tile, k) + lane;
+    const HcutScratch hs(scratch, gridDim.x, S);
+    const real* __restrict__ m1 = hs.map(tile, j - 1);
+    const real* __restrict__ m2 = hs.map(tile, j);
+    real* __restrict__ mc = hs.comp(tile, k);
     // every operand is loaded ONCE into registers before the loops that use it (a load inside a loop nest is re-issued per
     // use once a store to the composed map stands between two uses: the first form of this kernel had 640 loads and 500 waits)
     real G1[21], H2[21];
-#pragma unroll
-    for (int e = 0; e < 21; e++) { G1[e] = m1[(size_t)(57 + e) * TILE]; H2[e] = m2[(size_t)e * TILE]; }
+    hc_load<21>(m1, HC_GAM, lane, G1);
+    hc_load<21>(m2, HC_H, lane, H2);
     // X = I + Gam1 H2 (both wavefronts: the elimination is the same, only the right-hand sides differ)
     real X[6][6];
 #pragma unroll
@@ -423,8 +497,7 @@ __global__ __launch_bounds__(2 * TILE) void k_hcut_pair(int S, real* __restrict_
         }
     if (wv == 0) {   // Z = W Phi1;  Phi = Phi2 Z;  H = H1 + Phi1^T (H2 Z);  eta = eta1 + Z^T (eta2 + H2 beta1)
         real Z[6][6];
-#pragma unroll
-        for (int e = 0; e < 36; e++) Z[e / 6][e % 6] = m1[(size_t)(21 + e) * TILE];
+        hc_load<36>(m1, HC_PHI, lane, &Z[0][0]);
         hc_solve6(X, Z);
         real Y[6][6], v[6];                    // Y = H2 Z,  v = eta2 + H2 beta1
 #pragma unroll
@@ -438,8 +511,8 @@ __global__ __launch_bounds__(2 * TILE) void k_hcut_pair(int S, real* __restrict_
             }
         if (AFFINE) {
             real b1[6];
-#pragma unroll
-            for (int i = 0; i < 6; i++) { b1[i] = m1[(size_t)(84 + i) * TILE]; v[i] = m2[(size_t)(78 + i) * TILE]; }
+            hc_load<6>(m1, HC_BETA, lane, b1);
+            hc_load<6>(m2, HC_ETA, lane, v);
 #pragma unroll
             for (int i = 0; i < 6; i++)
 #pragma unroll
@@ -447,8 +520,7 @@ __global__ __launch_bounds__(2 * TILE) void k_hcut_pair(int S, real* __restrict_
         }
         {
             real F2[36], Fc[36];
-#pragma unroll
-            for (int e = 0; e < 36; e++) F2[e] = m2[(size_t)(21 + e) * TILE];
+            hc_load<36>(m2, HC_PHI, lane, F2);
 #pragma unroll
             for (int i = 0; i < 6; i++)
 #pragma unroll
@@ -458,14 +530,11 @@ __global__ __launch_bounds__(2 * TILE) void k_hcut_pair(int S, real* __restrict_
                     for (int q = 0; q < 6; q++) a += F2[i * 6 + q] * Z[q][c];
                     Fc[i * 6 + c] = a;
                 }
-#pragma unroll
-            for (int e = 0; e < 36; e++) mc[(size_t)(21 + e) * TILE] = Fc[e];
+            hc_store<36>(mc, HC_PHI, lane, Fc);
         }
         real F1[36], Hc[21];
-#pragma unroll
-        for (int e = 0; e < 36; e++) F1[e] = m1[(size_t)(21 + e) * TILE];
-#pragma unroll
-        for (int e = 0; e < 21; e++) Hc[e] = m1[(size_t)e * TILE];
+        hc_load<36>(m1, HC_PHI, lane, F1);
+        hc_load<21>(m1, HC_H, lane, Hc);
 #pragma unroll
         for (int i = 0; i < 6; i++)
 #pragma unroll
@@ -475,18 +544,15 @@ __global__ __launch_bounds__(2 * TILE) void k_hcut_pair(int S, real* __restrict_
                 for (int q = 0; q < 6; q++) a += F1[q * 6 + i] * Y[q][c];
                 Hc[sidx(i, c)] = a;
             }
-#pragma unroll
-        for (int e = 0; e < 21; e++) mc[(size_t)e * TILE] = Hc[e];
+        hc_store<21>(mc, HC_H, lane, Hc);
         if (AFFINE) {
             real ec[6];
-#pragma unroll
-            for (int c = 0; c < 6; c++) ec[c] = m1[(size_t)(78 + c) * TILE];
+            hc_load<6>(m1, HC_ETA, lane, ec);
 #pragma unroll
             for (int c = 0; c < 6; c++)
 #pragma unroll
                 for (int q = 0; q < 6; q++) ec[c] += Z[q][c] * v[q];
-#pragma unroll
-            for (int c = 0; c < 6; c++) mc[(size_t)(78 + c) * TILE] = ec[c];
+            hc_store<6>(mc, HC_ETA, lane, ec);
         }
     } else {         // Z = W [Gam1 | beta1 - Gam1 eta2];  Gam = Gam2 + Phi2 Z Phi2^T;  beta = beta2 + Phi2 z
         real Z[6][7];
@@ -498,8 +564,9 @@ __global__ __launch_bounds__(2 * TILE) void k_hcut_pair(int S, real* __restrict_
         }
         if (AFFINE) {
             real e2[6];
+            hc_load<6>(m2, HC_ETA, lane, e2);
 #pragma unroll
-            for (int i = 0; i < 6; i++) { e2[i] = m2[(size_t)(78 + i) * TILE]; Z[i][6] = m1[(size_t)(84 + i) * TILE]; }
+            for (int i = 0; i < 6; i++) Z[i][6] = m1[(size_t)(HC_BETA + i) * TILE + lane];
 #pragma unroll
             for (int i = 0; i < 6; i++)
 #pragma unroll
@@ -507,10 +574,8 @@ __global__ __launch_bounds__(2 * TILE) void k_hcut_pair(int S, real* __restrict_
         }
         hc_solve6n<7>(X, Z);
         real F2[36], Y[6][6], Gc[21];          // Y = Phi2 Z
-#pragma unroll
-        for (int e = 0; e < 36; e++) F2[e] = m2[(size_t)(21 + e) * TILE];
-#pragma unroll
-        for (int e = 0; e < 21; e++) Gc[e] = m2[(size_t)(57 + e) * TILE];
+        hc_load<36>(m2, HC_PHI, lane, F2);
+        hc_load<21>(m2, HC_GAM, lane, Gc);
 #pragma unroll
         for (int i = 0; i < 6; i++)
 #pragma unroll
@@ -529,18 +594,15 @@ __global__ __launch_bounds__(2 * TILE) void k_hcut_pair(int S, real* __restrict_
                 for (int q = 0; q < 6; q++) a += Y[i][q] * F2[c * 6 + q];
                 Gc[sidx(i, c)] = a;
             }
-#pragma unroll
-        for (int e = 0; e < 21; e++) mc[(size_t)(57 + e) * TILE] = Gc[e];
+        hc_store<21>(mc, HC_GAM, lane, Gc);
         if (AFFINE) {
             real bc[6];
-#pragma unroll
-            for (int i = 0; i < 6; i++) bc[i] = m2[(size_t)(84 + i) * TILE];
+            hc_load<6>(m2, HC_BETA, lane, bc);
 #pragma unroll
             for (int i = 0; i < 6; i++)
 #pragma unroll
                 for (int q = 0; q < 6; q++) bc[i] += F2[i * 6 + q] * Z[q][6];
-#pragma unroll
-            for (int i = 0; i < 6; i++) mc[(size_t)(84 + i) * TILE] = bc[i];
+            hc_store<6>(mc, HC_BETA, lane, bc);
         }
     }
 }
@@ -549,28 +611,18 @@ __global__ __launch_bounds__(2 * TILE) void k_hcut_pair(int S, real* __restrict_
 template <bool AFFINE>
 __global__ __launch_bounds__(TILE) void k_track_hcut_chain(int S, real* __restrict__ scratch, int npairs) {
     const int tile = blockIdx.x, lane = threadIdx.x;
-    real* maps0 = scratch + (size_t)tile * S * HC_MAP * TILE;
-    real* bnd0 = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + (size_t)tile * S * HC_BND * TILE;
+    const HcutScratch hs(scratch, gridDim.x, S);
     real P[21], p[6];
-#pragma unroll
-    for (int e = 0; e < 21; e++) P[e] = bnd0[((size_t)(S - 1) * HC_BND + e) * TILE + lane];   // P at the first stage of the last segment
-#pragma unroll
-    for (int e = 0; e < 6; e++) p[e] = AFFINE ? bnd0[((size_t)(S - 1) * HC_BND + 21 + e) * TILE + lane] : R(0.0);
+    hc_load_value<AFFINE>(hs.bnd(tile, S - 1), lane, P, p);                 // at the first stage of the last segment
     int seg = S - 2;
     for (int hop = 0;; hop++) {
-        real* bnd = bnd0 + (size_t)seg * HC_BND * TILE;
-#pragma unroll
-        for (int e = 0; e < 21; e++) bnd[(size_t)e * TILE + lane] = P[e];   // the value function at the END of segment seg
-        if (AFFINE) {
-#pragma unroll
-            for (int e = 0; e < 6; e++) bnd[(size_t)(21 + e) * TILE + lane] = p[e];
-        }
+        hc_store_value<AFFINE>(hs.bnd(tile, seg), lane, P, p);              // the value function at the END of segment seg
         if (seg == 0) break;                                                // nobody needs P at stage 0
         if (hop < npairs) {
-            hcut_hop<AFFINE>(hcut_comp(scratch, gridDim.x, S, tile, hop), lane, P, p);   // over segments seg - 1 and seg
+            hcut_hop<AFFINE>(hs.comp(tile, hop), lane, P, p);               // over segments seg - 1 and seg
             seg -= 2;
         } else {
-            hcut_hop<AFFINE>(maps0 + (size_t)seg * HC_MAP * TILE, lane, P, p);
+            hcut_hop<AFFINE>(hs.map(tile, seg), lane, P, p);
             seg -= 1;
         }
     }
@@ -580,21 +632,11 @@ __global__ __launch_bounds__(TILE) void k_track_hcut_chain(int S, real* __restri
 template <bool AFFINE>
 __global__ __launch_bounds__(TILE) void k_hcut_odd(int S, real* __restrict__ scratch) {
     const int tile = blockIdx.x, lane = threadIdx.x, j = S - 2 - 2 * (int)blockIdx.y;
-    real* bnd0 = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + (size_t)tile * S * HC_BND * TILE;
-    const real* bj = bnd0 + (size_t)j * HC_BND * TILE;
+    const HcutScratch hs(scratch, gridDim.x, S);
     real P[21], p[6];
-#pragma unroll
-    for (int e = 0; e < 21; e++) P[e] = bj[(size_t)e * TILE + lane];
-#pragma unroll
-    for (int e = 0; e < 6; e++) p[e] = AFFINE ? bj[(size_t)(21 + e) * TILE + lane] : R(0.0);
-    hcut_hop<AFFINE>(scratch + ((size_t)tile * S + j) * HC_MAP * TILE, lane, P, p);
-    real* bo = bnd0 + (size_t)(j - 1) * HC_BND * TILE;
-#pragma unroll
-    for (int e = 0; e < 21; e++) bo[(size_t)e * TILE + lane] = P[e];
-    if (AFFINE) {
-#pragma unroll
-        for (int e = 0; e < 6; e++) bo[(size_t)(21 + e) * TILE + lane] = p[e];
-    }
+    hc_load_value<AFFINE>(hs.bnd(tile, j), lane, P, p);
+    hcut_hop<AFFINE>(hs.map(tile, j), lane, P, p);
+    hc_store_value<AFFINE>(hs.bnd(tile, j - 1), lane, P, p);
 }
 
 // The chain on several wavefronts per tile (round 5; the kernel keeps the name of its first form, k_hcut_chain6).  A hop of
@@ -614,7 +656,7 @@ __device__ __forceinline__ void hcut_hop_cols(const real* __restrict__ m, int la
         for (int i = 0; i < 6; i++) {
             real a = i == J0 + c ? R(1.0) : R(0.0);
 #pragma unroll
-            for (int q = 0; q < 6; q++) a += m[(size_t)(57 + (i <= q ? sidx(i, q) : sidx(q, i))) * TILE + lane] * hc_sym(P, q, J0 + c);
+            for (int q = 0; q < 6; q++) a += m[(size_t)(HC_GAM + (i <= q ? sidx(i, q) : sidx(q, i))) * TILE + lane] * hc_sym(P, q, J0 + c);
             shX[J0 + c][i][lane] = a;
         }
     }
@@ -624,8 +666,8 @@ __device__ __forceinline__ void hcut_hop_cols(const real* __restrict__ m, int la
     for (int i = 0; i < 6; i++) {
 #pragma unroll
         for (int j = 0; j < 6; j++) X[i][j] = shX[j][i][lane];
-        f[i][0] = m[(size_t)(21 + i * 6 + J0) * TILE + lane];        // Phi[i][J0], Phi[i][J0 + 1]
-        f[i][1] = m[(size_t)(21 + i * 6 + J0 + 1) * TILE + lane];
+        f[i][0] = m[(size_t)(HC_PHI + i * 6 + J0) * TILE + lane];        // Phi[i][J0], Phi[i][J0 + 1]
+        f[i][1] = m[(size_t)(HC_PHI + i * 6 + J0 + 1) * TILE + lane];
     }
     hc_solve6n<2>(X, f);                                             // columns J0, J0 + 1 of (I + Gam P)^-1 Phi
     real v[6];
@@ -634,7 +676,7 @@ __device__ __forceinline__ void hcut_hop_cols(const real* __restrict__ m, int la
         for (int i = 0; i < 6; i++) {
             real a = p[i];
 #pragma unroll
-            for (int q = 0; q < 6; q++) a += hc_sym(P, i, q) * m[(size_t)(84 + q) * TILE + lane];
+            for (int q = 0; q < 6; q++) a += hc_sym(P, i, q) * m[(size_t)(HC_BETA + q) * TILE + lane];
             v[i] = a;
         }
     }
@@ -651,19 +693,19 @@ __device__ __forceinline__ void hcut_hop_cols(const real* __restrict__ m, int la
             z[i] = a;
         }
         if (AFFINE) {   // p_J <- eta_J + F[:, J]^T (p + P beta)
-            real a = m[(size_t)(78 + J) * TILE + lane];
+            real a = m[(size_t)(HC_ETA + J) * TILE + lane];
 #pragma unroll
             for (int q = 0; q < 6; q++) a += f[q][c] * v[q];
-            shP[21 + J][lane] = a;
+            shP[HC_Bp + J][lane] = a;
         }
         // entries (i, J), i <= J, of P <- H + Phi^T Z
 #pragma unroll
         for (int i = 0; i < 6; i++) {
             if (i > J) continue;
-            real a = m[(size_t)sidx(i, J) * TILE + lane];
+            real a = m[(size_t)(HC_H + sidx(i, J)) * TILE + lane];
 #pragma unroll
-            for (int q = 0; q < 6; q++) a += m[(size_t)(21 + q * 6 + i) * TILE + lane] * z[q];
-            shP[sidx(i, J)][lane] = a;
+            for (int q = 0; q < 6; q++) a += m[(size_t)(HC_PHI + q * 6 + i) * TILE + lane] * z[q];
+            shP[HC_BP + sidx(i, J)][lane] = a;
         }
     }
 }
@@ -682,35 +724,23 @@ __global__ __launch_bounds__(4 * TILE) void k_hcut_chain6(int S, real* __restric
     __shared__ real shX[6][6][TILE];          // X = I + Gam P: [column][row][lane]
     __shared__ real shP[HC_BND][TILE];        // the new value function: P (upper triangle), p
     const int tile = blockIdx.x, lane = threadIdx.x & (TILE - 1), wj = threadIdx.x >> 6;   // wavefront wj < 3 owns columns 2 wj, 2 wj + 1; 3 loads
-    real* maps0 = scratch + (size_t)tile * S * HC_MAP * TILE;
-    real* bnd0 = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + (size_t)tile * S * HC_BND * TILE;
-    constexpr int NV = AFFINE ? HC_MAP : 78;   // values of a map that are used
+    const HcutScratch hs(scratch, gridDim.x, S);
+    constexpr int NV = AFFINE ? HC_MAP : HC_ETA;   // values of a map that are used
     auto stage_map = [&](int seg, int buf) {   // loader: map of segment seg -> shM[buf]
-        const real* m = maps0 + (size_t)seg * HC_MAP * TILE;
+        const real* m = hs.map(tile, seg);
 #pragma unroll 6
         for (int e = 0; e < NV; e++) shM[buf][e][lane] = m[(size_t)e * TILE + lane];
     };
     real P[21], p[6];
     if (wj < 3) {
-#pragma unroll
-        for (int e = 0; e < 21; e++) P[e] = bnd0[((size_t)(S - 1) * HC_BND + e) * TILE + lane];   // P at the first stage of the last segment
-#pragma unroll
-        for (int e = 0; e < 6; e++) p[e] = AFFINE ? bnd0[((size_t)(S - 1) * HC_BND + 21 + e) * TILE + lane] : R(0.0);
+        hc_load_value<AFFINE>(hs.bnd(tile, S - 1), lane, P, p);            // at the first stage of the last segment
     } else if (S >= 3) {
         stage_map(S - 2, 0);
     }
     __syncthreads();
     int buf = 0;
     for (int seg = S - 2; seg >= 0; seg--, buf ^= 1) {
-        if (wj == 0) {   // the value function at the END of segment seg
-            real* bnd = bnd0 + (size_t)seg * HC_BND * TILE;
-#pragma unroll
-            for (int e = 0; e < 21; e++) bnd[(size_t)e * TILE + lane] = P[e];
-            if (AFFINE) {
-#pragma unroll
-                for (int e = 0; e < 6; e++) bnd[(size_t)(21 + e) * TILE + lane] = p[e];
-            }
-        }
+        if (wj == 0) hc_store_value<AFFINE>(hs.bnd(tile, seg), lane, P, p);   // the value function at the END of segment seg
         if (seg == 0) break;                                              // nobody needs P at stage 0
         const real* m = &shM[buf][0][0];
         switch (wj) {   // wave-uniform: the columns are compile-time indices into the register arrays
@@ -723,12 +753,12 @@ __global__ __launch_bounds__(4 * TILE) void k_hcut_chain6(int S, real* __restric
                 break;
         }
         __syncthreads();
-        if (wj < 3) {
+        if (wj < 3) {   // the new value function, laid out in LDS like a boundary
 #pragma unroll
-            for (int e = 0; e < 21; e++) P[e] = shP[e][lane];
+            for (int e = 0; e < 21; e++) P[e] = shP[HC_BP + e][lane];
             if (AFFINE) {
 #pragma unroll
-                for (int e = 0; e < 6; e++) p[e] = shP[21 + e][lane];
+                for (int e = 0; e < 6; e++) p[e] = shP[HC_Bp + e][lane];
             }
         }
     }
@@ -741,40 +771,10 @@ __global__ __launch_bounds__(TILE) void k_track_hcut_gains(KConst k, int S, cons
                                                            int* __restrict__ status) {
     const int tile = blockIdx.x, seg = blockIdx.y, lane = threadIdx.x, T = k.T;
     const int t_lo = hcut_cut(T, S, seg), t_hi = hcut_cut(T, S, seg + 1);
-    const real* bnd = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + ((size_t)tile * S + seg) * HC_BND * TILE;
-    real P[21], p[6], Qb[21], xs[6];
-    int flags = 0;
-#pragma unroll
-    for (int e = 0; e < 21; e++) P[e] = bnd[(size_t)e * TILE + lane];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        p[i] = R(0.0);
-#pragma unroll
-        for (int j = i; j < 6; j++) Qb[sidx(i, j)] = k.Q[i * 6 + j];
-    }
-    StageIn<XT> cur, nxt;
-    real x0r[6];
-    stage_x0(x_opt0, tile, lane, t_lo, x0r);
-    stage_fetch<false>(x, u, tile, T, t_hi - 1, lane, cur);
-    for (int t = t_hi - 1; t >= t_lo; t--) {
-        stage_fetch<false>(x, u, tile, T, t > t_lo ? t - 1 : t, lane, nxt);
-        stage_state(cur, x0r, t, xs);
-        const SC s = trig(xs[3], xs[5]);
-        Lin l = linearise(k, xs, cur.u0, s);
-        track_lin_fields(l, [](int, real& v) { bw_opaque(v); });   // the cut of k_track_hcut_gains2: same roundings
-        real zz = R(0.0);
-        bw_opaque(zz);
-        const real z6[6] = {zz, zz, zz, zz, zz, zz}, z2[2] = {zz, zz};
-        const StageFlags fl = lqr_stage(k, l, P, p, Qb, zz, zz, zz, z6, z2, [&](int c, real a, real b) {
-            if (c >= 1) {
-                Kout[tix<12>(tile, T, t, c - 1, lane)] = a;
-                Kout[tix<12>(tile, T, t, 5 + c, lane)] = b;
-            }
-        });
-        if (fl.singular) flags |= AOC_ST_SINGULAR;
-        if (fl.regularised) flags |= AOC_ST_REGULARISED;
-        cur = nxt;
-    }
+    const HcutScratch hs(scratch, gridDim.x, S);
+    real P[21];
+    hc_load<21>(hs.bnd(tile, seg), HC_BP, lane, P);
+    const int flags = hcut_track_segment(k, x, u, x_opt0, tile, lane, t_lo, t_hi, P, Kout);
     if (status && flags) atomicOr(&status[tile * TILE + lane], flags);
 }
 
@@ -820,28 +820,18 @@ __device__ __forceinline__ int hcut_track_recursion(const KConst& k, int tile, i
     real p[6], Qb[21];
     int flags = 0;
 #pragma unroll
-    for (int i = 0; i < 6; i++) {
-        p[i] = R(0.0);
+    for (int i = 0; i < 6; i++) p[i] = R(0.0);
+#pragma unroll
+    for (int i = 0; i < 6; i++)
 #pragma unroll
         for (int j = i; j < 6; j++) Qb[sidx(i, j)] = k.Q[i * 6 + j];
-    }
     for (int j = 0; j < n + 1; j++) {
         if (j >= 1) {
             const int t = t_hi - j;
             Lin l;
             real(*src)[TILE][2] = sh[(j - 1) & 1];
             track_lin_fields(l, [&](int f, real& v) { v = src[f >> 1][lane][f & 1]; });
-            real zz = R(0.0);
-            bw_opaque(zz);
-            const real z6[6] = {zz, zz, zz, zz, zz, zz}, z2[2] = {zz, zz};
-            const StageFlags fl = lqr_stage(k, l, P, p, Qb, zz, zz, zz, z6, z2, [&](int c, real a, real b) {
-                if (c >= 1) {
-                    Kout[tix<12>(tile, T, t, c - 1, lane)] = a;
-                    Kout[tix<12>(tile, T, t, 5 + c, lane)] = b;
-                }
-            });
-            if (fl.singular) flags |= AOC_ST_SINGULAR;
-            if (fl.regularised) flags |= AOC_ST_REGULARISED;
+            flags |= track_gain_stage(k, l, P, p, Qb, Kout, tile, T, t, lane);
         }
         __syncthreads();
     }
@@ -859,8 +849,9 @@ __global__ __launch_bounds__(3 * TILE) void k_track_hcut_map3(KConst kc, int S, 
     const bool last = seg == S - 1;
     if (last && wv == 2) return;   // (a barrier waits for the wavefronts that are still there)
     const int t_lo = hcut_cut(T, S, seg), t_hi = hcut_cut(T, S, seg + 1), n = t_hi - t_lo;
-    real* maps = scratch + ((size_t)tile * S + seg) * HC_MAP * TILE;
-    real* bnd = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + ((size_t)tile * S + seg) * HC_BND * TILE;
+    const HcutScratch hs(scratch, gridDim.x, S);
+    real* const maps = hs.map(tile, seg);
+    real* const bnd = hs.bnd(tile, seg);
     KConst k = kc;
     if (wv == 0) {   // linearisation, one stage ahead of the others
         TrigK<real> tk;
@@ -876,8 +867,7 @@ __global__ __launch_bounds__(3 * TILE) void k_track_hcut_map3(KConst kc, int S, 
 #pragma unroll
             for (int j = i; j < 6; j++) P[sidx(i, j)] = k.QT[i * 6 + j];
         const int flags = hcut_track_recursion(k, tile, lane, t_lo, t_hi, P, Kout, shL);
-#pragma unroll
-        for (int e = 0; e < 21; e++) bnd[(size_t)e * TILE + lane] = P[e];
+        hc_store<21>(bnd, HC_BP, lane, P);
 #pragma unroll
         for (int j = 0; j < 12; j++) Kout[tix<12>(tile, T, T - 1, j, lane)] = R(0.0);  // KK[:,:,T-1] stays 0 (:700)
         if (status && flags) atomicOr(&status[tile * TILE + lane], flags);
@@ -888,7 +878,8 @@ __global__ __launch_bounds__(3 * TILE) void k_track_hcut_map3(KConst kc, int S, 
 #pragma unroll
         for (int i = 0; i < 6; i++)
 #pragma unroll
-            for (int j = i; j < 6; j++) { Qb[sidx(i, j)] = k.Q[i * 6 + j]; H[sidx(i, j)] = R(0.0); }
+            for (int j = i; j < 6; j++) Qb[sidx(i, j)] = k.Q[i * 6 + j];
+        hc_init_h(H, nullptr);
         StageFlags fl{false, false};
         for (int j = 0; j < n + 2; j++) {
             if (j >= 1 && j <= n) {
@@ -902,15 +893,11 @@ __global__ __launch_bounds__(3 * TILE) void k_track_hcut_map3(KConst kc, int S, 
             }
             __syncthreads();
         }
-#pragma unroll
-        for (int e = 0; e < 21; e++) maps[(size_t)e * TILE + lane] = H[e];
+        hc_store_h(maps, lane, H, nullptr);
         if (status && fl.singular) atomicOr(&status[tile * TILE + lane], (int)AOC_ST_SINGULAR);
     } else {         // the Phi half, two steps behind
         real Phi[36], Gam[21];
-#pragma unroll
-        for (int e = 0; e < 21; e++) Gam[e] = R(0.0);
-#pragma unroll
-        for (int e = 0; e < 36; e++) Phi[e] = (e % 7 == 0) ? R(1.0) : R(0.0);
+        hc_init_phi(Phi, Gam, nullptr);
         for (int j = 0; j < n + 2; j++) {
             if (j >= 2) {
                 HcutMid m;
@@ -920,10 +907,7 @@ __global__ __launch_bounds__(3 * TILE) void k_track_hcut_map3(KConst kc, int S, 
             }
             __syncthreads();
         }
-#pragma unroll
-        for (int e = 0; e < 36; e++) maps[(size_t)(21 + e) * TILE + lane] = Phi[e];
-#pragma unroll
-        for (int e = 0; e < 21; e++) maps[(size_t)(57 + e) * TILE + lane] = Gam[e];
+        hc_store_phi(maps, lane, Phi, Gam, nullptr);
     }
 }
 
@@ -943,10 +927,8 @@ __global__ __launch_bounds__(2 * TILE) void k_track_hcut_gains2(KConst kc, int S
         return;
     }
     if (AOC_PIN) pin_consts<DIAG>(k);
-    const real* bnd = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + ((size_t)tile * S + seg) * HC_BND * TILE;
     real P[21];
-#pragma unroll
-    for (int e = 0; e < 21; e++) P[e] = bnd[(size_t)e * TILE + lane];
+    hc_load<21>(HcutScratch(scratch, gridDim.x, S).bnd(tile, seg), HC_BP, lane, P);
     const int flags = hcut_track_recursion(k, tile, lane, t_lo, t_hi, P, Kout, shL);
     if (status && flags) atomicOr(&status[tile * TILE + lane], flags);
 }
@@ -975,20 +957,29 @@ __global__ __launch_bounds__(2 * TILE) void k_track_hcut_gains2(KConst kc, int S
 // Scratch behind the Gauss-Newton layout (hcut_scratch_bytes): per (tile, segment) the costate map (36 + 6) and lambda at
 // the segment's first stage (6); per lane the flags of the cut (merged into `status` at the end); per tile the verdict.
 // ---------------------------------------------------------------------------------------------
-constexpr int HC_LMAP = 36 + 6, HC_LB = 6;
-static size_t hcut_full_scratch_bytes(int ntiles, int S) {
-    return hcut_scratch_bytes(ntiles, S) + (size_t)ntiles * S * (HC_LMAP + HC_LB) * TILE * sizeof(real) +
-           align_up((size_t)ntiles * TILE * sizeof(int), 16) + align_up((size_t)ntiles * sizeof(int), 16);
+constexpr int HC_LMAP = 36 + 6, HC_LB = 6;   // a costate map: M (row-major), c
+struct HcutFull {
+    real* lmap; real* lb; int* lane_flags; int* tile_flag; int trust;
+    __device__ __forceinline__ real* lmap_at(int tile, int S, int seg) const { return lmap + ((size_t)tile * S + seg) * HC_LMAP * TILE; }
+    __device__ __forceinline__ real* lb_at(int tile, int S, int seg) const { return lb + ((size_t)tile * S + seg) * HC_LB * TILE; }
+};
+// one walk over that layout: carves it out of `scratch` (if given) and returns its end, the bytes a full-Hessian pass takes
+static size_t hcut_full_layout(void* scratch, int ntiles, int S, HcutFull* out) {
+    size_t off = hcut_scratch_bytes(ntiles, S);
+    auto take = [&](size_t bytes) { char* q = scratch ? (char*)scratch + off : nullptr; off += bytes; return q; };
+    HcutFull f;
+    f.lmap = (real*)take((size_t)ntiles * S * HC_LMAP * TILE * sizeof(real));
+    f.lb = (real*)take((size_t)ntiles * S * HC_LB * TILE * sizeof(real));
+    f.lane_flags = (int*)take(align_up((size_t)ntiles * TILE * sizeof(int), 16));
+    f.tile_flag = (int*)take(align_up((size_t)ntiles * sizeof(int), 16));
+    f.trust = 0;
+    if (out) *out = f;
+    return off;
 }
-struct HcutFull { real* lmap; real* lb; int* lane_flags; int* tile_flag; int trust; };
+static size_t hcut_full_scratch_bytes(int ntiles, int S) { return hcut_full_layout(nullptr, ntiles, S, nullptr); }
 static HcutFull hcut_full_carve(void* scratch, int ntiles, int S) {
     HcutFull f;
-    char* q = (char*)scratch + hcut_scratch_bytes(ntiles, S);
-    f.lmap = (real*)q;          q += (size_t)ntiles * S * HC_LMAP * TILE * sizeof(real);
-    f.lb = (real*)q;            q += (size_t)ntiles * S * HC_LB * TILE * sizeof(real);
-    f.lane_flags = (int*)q;     q += align_up((size_t)ntiles * TILE * sizeof(int), 16);
-    f.tile_flag = (int*)q;
-    f.trust = 0;
+    hcut_full_layout(scratch, ntiles, S, &f);
     return f;
 }
 
@@ -1022,9 +1013,7 @@ __global__ __launch_bounds__(TILE) void k_bw_hcut_lam(KConst k, int S, const rea
 #pragma unroll
             for (int i = 0; i < 6; i++) lam[i] = al[i] + q[i];
         }
-        real* lb = hf.lb + ((size_t)tile * S + seg) * HC_LB * TILE;
-#pragma unroll
-        for (int i = 0; i < 6; i++) lb[(size_t)i * TILE + lane] = lam[i];
+        hc_store<6>(hf.lb_at(tile, S, seg), 0, lane, lam);
         return;
     }
     real M[6][6], c[6];      // M[:, j] = column j
@@ -1057,7 +1046,7 @@ __global__ __launch_bounds__(TILE) void k_bw_hcut_lam(KConst k, int S, const rea
 #pragma unroll
         for (int i = 0; i < 6; i++) c[i] = y[i] + q[i];
     }
-    real* lm = hf.lmap + ((size_t)tile * S + seg) * HC_LMAP * TILE;
+    real* lm = hf.lmap_at(tile, S, seg);
 #pragma unroll
     for (int i = 0; i < 6; i++) {
 #pragma unroll
@@ -1069,11 +1058,9 @@ __global__ __launch_bounds__(TILE) void k_bw_hcut_lam(KConst k, int S, const rea
 // lambda at the END of segment seg (= at the first stage of segment seg + 1), seg < S - 1: from lambda at the first stage of
 // the last segment down through the costate maps of the segments in between
 __device__ __forceinline__ void hcut_lambda_end(const HcutFull& hf, int tile, int S, int seg, int lane, real lam[6]) {
-    const real* lb = hf.lb + ((size_t)tile * S + (S - 1)) * HC_LB * TILE;
-#pragma unroll
-    for (int i = 0; i < 6; i++) lam[i] = lb[(size_t)i * TILE + lane];
+    hc_load<6>(hf.lb_at(tile, S, S - 1), 0, lane, lam);
     for (int sgm = S - 2; sgm > seg; sgm--) {
-        const real* lm = hf.lmap + ((size_t)tile * S + sgm) * HC_LMAP * TILE;
+        const real* lm = hf.lmap_at(tile, S, sgm);
         real y[6];
 #pragma unroll
         for (int i = 0; i < 6; i++) {
@@ -1087,6 +1074,32 @@ __device__ __forceinline__ void hcut_lambda_end(const HcutFull& hf, int tile, in
     }
 }
 
+// what the segment kernels do with the flags of a lane at the end (FULL: they wait in scratch: a lane the cut does not trust
+// gets the sequential kernel's own)
+template <bool FULL>
+__device__ __forceinline__ void hcut_bw_flags(const HcutFull& hf, int* __restrict__ status, int tile, int lane, int flags,
+                                              bool distrust, bool true_recursion) {
+    if (FULL) {
+        if (distrust) flags |= HC_DISTRUST | (true_recursion ? HC_WHY_TRUE : HC_WHY_MAP);
+        if (flags) atomicOr(&hf.lane_flags[tile * TILE + lane], flags);
+        if (__ballot(distrust) != 0ull && lane == 0) atomicOr(&hf.tile_flag[tile], 1);
+    } else if (status && flags) atomicOr(&status[tile * TILE + lane], flags);
+}
+// ... and the verdict of a true recursion (last segment, gains pass).  trust 0: a lane whose true recursion regularises or
+// meets a singular M; trust 1: the singular ones only (and whatever is not a number: its PD test fails at every stage and
+// the value function is checked here)
+template <bool FULL>
+__device__ __forceinline__ bool hcut_bw_distrust(const HcutFull& hf, int flags, const real P[21], bool bad_in) {
+    bool distrust = hf.trust ? (flags & AOC_ST_SINGULAR) != 0 : flags != 0;
+    if (FULL && hf.trust) {
+        bool finite = true;
+#pragma unroll
+        for (int e = 0; e < 21; e++) finite = finite && (P[e] - P[e] == R(0.0));
+        distrust = (distrust || !finite) && !bad_in;
+    }
+    return distrust;
+}
+
 // The Gauss-Newton backward pass of the Newton iteration with the horizon cut the same way (aoc_tuning.bw_hcut segments):
 // affine terms included (hcut_stage<true>), K~ stored as k_backward stores it.
 // y = 0: map of a segment (the last one: the plain recursion, gains final); y = 1 (second launch): gains from the boundary.
@@ -1097,8 +1110,9 @@ __global__ __launch_bounds__(TILE) void k_bw_hcut(KConst k, int S, const real* _
                                                   HcutFull hf = HcutFull{nullptr, nullptr, nullptr, nullptr, 0}) {
     const int tile = blockIdx.x, seg = blockIdx.y, lane = threadIdx.x, T = k.T;
     const int t_lo = hcut_cut(T, S, seg), t_hi = hcut_cut(T, S, seg + 1);   // stages t_hi-1 .. t_lo
-    real* maps = scratch + ((size_t)tile * S + seg) * HC_MAP * TILE;
-    real* bnd = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + ((size_t)tile * S + seg) * HC_BND * TILE;
+    const HcutScratch hs(scratch, gridDim.x, S);
+    real* const maps = hs.map(tile, seg);
+    real* const bnd = hs.bnd(tile, seg);
     real P[21], p[6], lam[6], Qb[21], xs[6];
     int flags = 0;
     bool distrust = false;     // FULL: a stage whose M is not positive definite or singular (see above)
@@ -1112,15 +1126,8 @@ __global__ __launch_bounds__(TILE) void k_bw_hcut(KConst k, int S, const real* _
         if (FULL) hcut_lambda_end(hf, tile, S, seg, lane, lam);     // lambda_{t_hi}
     }
     if (GAINS || last) {
-        if (GAINS) {   // this segment's end value, from the chain
-            const real* b2 = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + ((size_t)tile * S + seg) * HC_BND * TILE;
-#pragma unroll
-            for (int e = 0; e < 21; e++) P[e] = b2[(size_t)e * TILE + lane];
-#pragma unroll
-            for (int e = 0; e < 6; e++) p[e] = b2[(size_t)(21 + e) * TILE + lane];
-        } else {
-            bw_terminal<DIAG, RPT>(k, ref, x, x0, tile, lane, P, p, lam, Qb);
-        }
+        if (GAINS) hc_load_value<true>(bnd, lane, P, p);   // this segment's end value, from the chain
+        else bw_terminal<DIAG, RPT>(k, ref, x, x0, tile, lane, P, p, lam, Qb);
         StageIn<XT> cur, nxt;
         real x0r[6];
         stage_x0(x0, tile, lane, t_lo, x0r);
@@ -1129,7 +1136,7 @@ __global__ __launch_bounds__(TILE) void k_bw_hcut(KConst k, int S, const real* _
             stage_fetch<true>(x, u, tile, T, t > t_lo ? t - 1 : t, lane, nxt);
             stage_state(cur, x0r, t, xs);
             const real u0 = cur.u0, u1 = cur.u1;
-            if (FULL) { const real chk = (u0 + u1) + ((xs[0] + xs[1]) + (xs[2] + xs[3]) + (xs[4] + xs[5])); bad_in = bad_in || !(chk - chk == R(0.0)); }
+            if (FULL) bad_in = bad_in || hc_bad_input(xs, u0, u1);
             BwIn in;
             bw_produce<DIAG, RPT, FULL, FULL>(k, ref, tile, lane, t, xs, u0, u1, lam, in);
             bw_fields<FULL>(in, [](int, real& v) { bw_opaque(v); });   // the cut of k_bw_hcut_map3 / _gains2: same roundings
@@ -1140,29 +1147,12 @@ __global__ __launch_bounds__(TILE) void k_bw_hcut(KConst k, int S, const real* _
             if (fl.singular) flags |= AOC_ST_SINGULAR;
             if (fl.regularised) flags |= AOC_ST_REGULARISED;
         }
-        // trust 0: a lane whose true recursion regularises or meets a singular M; trust 1: the singular ones only (and
-        // whatever is not a number: its PD test fails at every stage and the value function is checked below)
-        distrust = hf.trust ? (flags & AOC_ST_SINGULAR) != 0 : flags != 0;
-        if (FULL && hf.trust) {
-            bool finite = true;
-#pragma unroll
-            for (int e = 0; e < 21; e++) finite = finite && (P[e] - P[e] == R(0.0));
-            distrust = (distrust || !finite) && !bad_in;
-        }
-        if (!GAINS) {   // (P, p) at the first stage of the last segment
-#pragma unroll
-            for (int e = 0; e < 21; e++) bnd[(size_t)e * TILE + lane] = P[e];
-#pragma unroll
-            for (int e = 0; e < 6; e++) bnd[(size_t)(21 + e) * TILE + lane] = p[e];
-        }
+        distrust = hcut_bw_distrust<FULL>(hf, flags, P, bad_in);
+        if (!GAINS) hc_store_value<true>(bnd, lane, P, p);   // (P, p) at the first stage of the last segment
     } else {
         real H[21], Phi[36], Gam[21], eta[6], beta[6];
-#pragma unroll
-        for (int e = 0; e < 21; e++) { H[e] = R(0.0); Gam[e] = R(0.0); }
-#pragma unroll
-        for (int e = 0; e < 36; e++) Phi[e] = (e % 7 == 0) ? R(1.0) : R(0.0);
-#pragma unroll
-        for (int e = 0; e < 6; e++) { eta[e] = R(0.0); beta[e] = R(0.0); }
+        hc_init_h(H, eta);
+        hc_init_phi(Phi, Gam, beta);
         StageFlags fl{false, false};
         StageIn<XT> cur, nxt;
         real x0r[6];
@@ -1176,14 +1166,10 @@ __global__ __launch_bounds__(TILE) void k_bw_hcut(KConst k, int S, const real* _
             bw_produce<DIAG, RPT, FULL, FULL>(k, ref, tile, lane, t, xs, u0, u1, lam, in);
             bw_fields<FULL>(in, [](int, real& v) { bw_opaque(v); });
             if (FULL) {
-                const real chk = (u0 + u1) + ((xs[0] + xs[1]) + (xs[2] + xs[3]) + (xs[4] + xs[5]));
-                bad_in = bad_in || !(chk - chk == R(0.0));
+                bad_in = bad_in || hc_bad_input(xs, u0, u1);
                 bw_derive<true>(in);
                 real Qs[21];
-#pragma unroll
-                for (int e = 0; e < 21; e++) Qs[e] = Qb[e];
-                Qs[sidx(2, 2)] += in.dq[0]; Qs[sidx(2, 3)] += in.dq[1]; Qs[sidx(2, 5)] += in.dq[2];
-                Qs[sidx(3, 3)] += in.dq[3]; Qs[sidx(3, 5)] += in.dq[4]; Qs[sidx(5, 5)] += in.dq[5];
+                bw_stage_q<true>(in, Qb, Qs);
                 hcut_stage<true, true>(k, in.l, H, Phi, Gam, Qs, fl, eta, beta, in.hq, in.hr, in.s02, in.s03, in.s05);
             } else {
                 hcut_stage<true>(k, in.l, H, Phi, Gam, Qb, fl, eta, beta, in.hq, in.hr);
@@ -1192,20 +1178,10 @@ __global__ __launch_bounds__(TILE) void k_bw_hcut(KConst k, int S, const real* _
         if (fl.singular) flags |= AOC_ST_SINGULAR;
         // (the maps raise no REGULARISED flag: the gains pass reports the true recursion)
         distrust = hf.trust ? (fl.singular && !bad_in) : (fl.singular || fl.regularised);
-#pragma unroll
-        for (int e = 0; e < 21; e++) maps[(size_t)e * TILE + lane] = H[e];
-#pragma unroll
-        for (int e = 0; e < 36; e++) maps[(size_t)(21 + e) * TILE + lane] = Phi[e];
-#pragma unroll
-        for (int e = 0; e < 21; e++) maps[(size_t)(57 + e) * TILE + lane] = Gam[e];
-#pragma unroll
-        for (int e = 0; e < 6; e++) { maps[(size_t)(78 + e) * TILE + lane] = eta[e]; maps[(size_t)(84 + e) * TILE + lane] = beta[e]; }
+        hc_store_h(maps, lane, H, eta);
+        hc_store_phi(maps, lane, Phi, Gam, beta);
     }
-    if (FULL) {   // the flags wait in scratch: a lane the cut does not trust gets the sequential kernel's own
-        if (distrust) flags |= HC_DISTRUST | ((GAINS || last) ? HC_WHY_TRUE : HC_WHY_MAP);
-        if (flags) atomicOr(&hf.lane_flags[tile * TILE + lane], flags);
-        if (__ballot(distrust) != 0ull && lane == 0) atomicOr(&hf.tile_flag[tile], 1);
-    } else if (status && flags) atomicOr(&status[tile * TILE + lane], flags);
+    hcut_bw_flags<FULL>(hf, status, tile, lane, flags, distrust, GAINS || last);
 }
 
 // The same on several wavefronts per (tile, segment), see k_track_hcut_map3: k_bw_hcut_map3 (producer: everything bw_produce
@@ -1228,7 +1204,7 @@ __device__ __forceinline__ bool hcut_bw_producer(const KConst& k, const TrigK<re
             stage_fetch<true>(x, u, tile, T, t > t_lo ? t - 1 : t, lane, nxt);
             stage_state(cur, x0r, t, xs);
             const real u0 = cur.u0, u1 = cur.u1;
-            if (FULL) { const real chk = (u0 + u1) + ((xs[0] + xs[1]) + (xs[2] + xs[3]) + (xs[4] + xs[5])); bad_in = bad_in || !(chk - chk == R(0.0)); }
+            if (FULL) bad_in = bad_in || hc_bad_input(xs, u0, u1);
             BwIn in;
             bw_produce<DIAG, RPT, FULL, FULL>(k, ref, tile, lane, t, xs, u0, u1, lam, in, tk);
             real(*dst)[TILE][2] = sh[j & 1];
@@ -1261,29 +1237,6 @@ __device__ __forceinline__ int hcut_bw_recursion(const KConst& k, int tile, int 
     }
     return flags;
 }
-// what k_bw_hcut does with the flags of a lane at the end (FULL: they wait in scratch, see there)
-template <bool FULL>
-__device__ __forceinline__ void hcut_bw_flags(const HcutFull& hf, int* __restrict__ status, int tile, int lane, int flags,
-                                              bool distrust, bool true_recursion) {
-    if (FULL) {
-        if (distrust) flags |= HC_DISTRUST | (true_recursion ? HC_WHY_TRUE : HC_WHY_MAP);
-        if (flags) atomicOr(&hf.lane_flags[tile * TILE + lane], flags);
-        if (__ballot(distrust) != 0ull && lane == 0) atomicOr(&hf.tile_flag[tile], 1);
-    } else if (status && flags) atomicOr(&status[tile * TILE + lane], flags);
-}
-// ... and with the verdict of a true recursion (last segment, gains pass)
-template <bool FULL>
-__device__ __forceinline__ bool hcut_bw_distrust(const HcutFull& hf, int flags, const real P[21], bool bad_in) {
-    bool distrust = hf.trust ? (flags & AOC_ST_SINGULAR) != 0 : flags != 0;
-    if (FULL && hf.trust) {
-        bool finite = true;
-#pragma unroll
-        for (int e = 0; e < 21; e++) finite = finite && (P[e] - P[e] == R(0.0));
-        distrust = (distrust || !finite) && !bad_in;
-    }
-    return distrust;
-}
-
 template <bool DIAG, bool RPT, typename XT, bool FULL>
 __global__ __launch_bounds__(3 * TILE) void k_bw_hcut_map3(KConst kc, int S, const real* __restrict__ ref, const XT* __restrict__ x,
                                                            const real* __restrict__ u, const real* __restrict__ x0,
@@ -1297,8 +1250,9 @@ __global__ __launch_bounds__(3 * TILE) void k_bw_hcut_map3(KConst kc, int S, con
     const bool last = seg == S - 1;
     if (last && wv == 2) return;   // (a barrier waits for the wavefronts that are still there)
     const int t_lo = hcut_cut(T, S, seg), t_hi = hcut_cut(T, S, seg + 1), n = t_hi - t_lo;
-    real* maps = scratch + ((size_t)tile * S + seg) * HC_MAP * TILE;
-    real* bnd = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + ((size_t)tile * S + seg) * HC_BND * TILE;
+    const HcutScratch hs(scratch, gridDim.x, S);
+    real* const maps = hs.map(tile, seg);
+    real* const bnd = hs.bnd(tile, seg);
     KConst k = kc;
     real P[21], p[6], lam[6], Qb[21];
     if (wv == 0) {   // everything that depends on the iterate and on the costate only, one stage ahead of the others
@@ -1316,21 +1270,17 @@ __global__ __launch_bounds__(3 * TILE) void k_bw_hcut_map3(KConst kc, int S, con
         const int flags = hcut_bw_recursion<FULL>(k, tile, lane, t_lo, t_hi, P, p, Qb, Kt, shB);
         bool bad_in = false;
         if (FULL) { __syncthreads(); bad_in = shBad[lane] != 0; }
-#pragma unroll
-        for (int e = 0; e < 21; e++) bnd[(size_t)e * TILE + lane] = P[e];
-#pragma unroll
-        for (int e = 0; e < 6; e++) bnd[(size_t)(21 + e) * TILE + lane] = p[e];
+        hc_store_value<true>(bnd, lane, P, p);
         hcut_bw_flags<FULL>(hf, status, tile, lane, flags, hcut_bw_distrust<FULL>(hf, flags, P, bad_in), true);
         return;
     }
     if (wv == 1) {   // the H half (and eta), one step behind the producer
         real H[21], eta[6];
 #pragma unroll
-        for (int i = 0; i < 6; i++) {
-            eta[i] = R(0.0);
+        for (int i = 0; i < 6; i++)
 #pragma unroll
-            for (int j = i; j < 6; j++) { Qb[sidx(i, j)] = k.Q[i * 6 + j]; H[sidx(i, j)] = R(0.0); }
-        }
+            for (int j = i; j < 6; j++) Qb[sidx(i, j)] = k.Q[i * 6 + j];
+        hc_init_h(H, eta);
         StageFlags fl{false, false};
         for (int j = 0; j < n + 2; j++) {
             if (j >= 1 && j <= n) {
@@ -1341,10 +1291,7 @@ __global__ __launch_bounds__(3 * TILE) void k_bw_hcut_map3(KConst kc, int S, con
                 if (FULL) {
                     bw_derive<true>(in);
                     real Qs[21];
-#pragma unroll
-                    for (int e = 0; e < 21; e++) Qs[e] = Qb[e];
-                    Qs[sidx(2, 2)] += in.dq[0]; Qs[sidx(2, 3)] += in.dq[1]; Qs[sidx(2, 5)] += in.dq[2];
-                    Qs[sidx(3, 3)] += in.dq[3]; Qs[sidx(3, 5)] += in.dq[4]; Qs[sidx(5, 5)] += in.dq[5];
+                    bw_stage_q<true>(in, Qb, Qs);
                     hcut_stage_h<true, true>(k, in.l, H, Qs, fl, m, eta, in.hq, in.hr, in.s02, in.s03, in.s05);
                 } else {
                     hcut_stage_h<true>(k, in.l, H, Qb, fl, m, eta, in.hq, in.hr);
@@ -1356,21 +1303,13 @@ __global__ __launch_bounds__(3 * TILE) void k_bw_hcut_map3(KConst kc, int S, con
         }
         bool bad_in = false;
         if (FULL) { __syncthreads(); bad_in = shBad[lane] != 0; }
-#pragma unroll
-        for (int e = 0; e < 21; e++) maps[(size_t)e * TILE + lane] = H[e];
-#pragma unroll
-        for (int e = 0; e < 6; e++) maps[(size_t)(78 + e) * TILE + lane] = eta[e];
+        hc_store_h(maps, lane, H, eta);
         // (the maps raise no REGULARISED flag: the gains pass reports the true recursion)
         const bool distrust = hf.trust ? (fl.singular && !bad_in) : (fl.singular || fl.regularised);
         hcut_bw_flags<FULL>(hf, status, tile, lane, fl.singular ? (int)AOC_ST_SINGULAR : 0, FULL && distrust, false);
     } else {         // the Phi half (and beta), two steps behind
         real Phi[36], Gam[21], beta[6];
-#pragma unroll
-        for (int e = 0; e < 21; e++) Gam[e] = R(0.0);
-#pragma unroll
-        for (int e = 0; e < 36; e++) Phi[e] = (e % 7 == 0) ? R(1.0) : R(0.0);
-#pragma unroll
-        for (int e = 0; e < 6; e++) beta[e] = R(0.0);
+        hc_init_phi(Phi, Gam, beta);
         for (int j = 0; j < n + 2; j++) {
             if (j >= 2) {
                 HcutMid m;
@@ -1381,12 +1320,7 @@ __global__ __launch_bounds__(3 * TILE) void k_bw_hcut_map3(KConst kc, int S, con
             __syncthreads();
         }
         if (FULL) __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 36; e++) maps[(size_t)(21 + e) * TILE + lane] = Phi[e];
-#pragma unroll
-        for (int e = 0; e < 21; e++) maps[(size_t)(57 + e) * TILE + lane] = Gam[e];
-#pragma unroll
-        for (int e = 0; e < 6; e++) maps[(size_t)(84 + e) * TILE + lane] = beta[e];
+        hc_store_phi(maps, lane, Phi, Gam, beta);
     }
 }
 
@@ -1411,16 +1345,12 @@ __global__ __launch_bounds__(2 * TILE) void k_bw_hcut_gains2(KConst kc, int S, c
         return;
     }
     if (AOC_PIN) pin_consts<DIAG>(k);
-    const real* b2 = scratch + (size_t)gridDim.x * S * HC_MAP * TILE + ((size_t)tile * S + seg) * HC_BND * TILE;
     real P[21], p[6], Qb[21];
 #pragma unroll
     for (int i = 0; i < 6; i++)
 #pragma unroll
         for (int j = i; j < 6; j++) Qb[sidx(i, j)] = k.Q[i * 6 + j];
-#pragma unroll
-    for (int e = 0; e < 21; e++) P[e] = b2[(size_t)e * TILE + lane];
-#pragma unroll
-    for (int e = 0; e < 6; e++) p[e] = b2[(size_t)(21 + e) * TILE + lane];
+    hc_load_value<true>(HcutScratch(scratch, gridDim.x, S).bnd(tile, seg), lane, P, p);
     const int flags = hcut_bw_recursion<FULL>(k, tile, lane, t_lo, t_hi, P, p, Qb, Kt, shB);
     bool bad_in = false;
     if (FULL) { __syncthreads(); bad_in = shBad[lane] != 0; }

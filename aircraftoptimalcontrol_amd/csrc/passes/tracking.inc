@@ -4,6 +4,31 @@
 // constant weights and S = 0, gains K (2x6), closed-loop nonlinear rollout.
 // ---------------------------------------------------------------------------------------------
 
+// a run-time zero: every gain kernel then compiles the same arithmetic for the affine terms (the tracking problem has
+// q = r = 0, S = 0)
+__device__ __forceinline__ real track_zero() {
+    real zz = R(0.0);
+    bw_opaque(zz);
+    return zz;
+}
+// One stage of the tracking gains, whichever kernel runs it: the Riccati stage on (P, p) with the run-time zero for the
+// affine terms, the gain columns 1..6 stored into Kout at sample t (no feed-forward column here); the status bits back.
+__device__ __forceinline__ int track_gain_stage(const KConst& k, const Lin& l, real P[21], real p[6], const real Qb[21],
+                                                real* __restrict__ Kout, int tile, int T, int t, int lane) {
+    const real zz = track_zero();
+    const real z6[6] = {zz, zz, zz, zz, zz, zz}, z2[2] = {zz, zz};
+    const StageFlags fl = lqr_stage(k, l, P, p, Qb, zz, zz, zz, z6, z2, [&](int c, real a, real b) {
+        if (c >= 1) {
+            Kout[tix<12>(tile, T, t, c - 1, lane)] = a;
+            Kout[tix<12>(tile, T, t, 5 + c, lane)] = b;
+        }
+    });
+    int flags = 0;
+    if (fl.singular) flags |= AOC_ST_SINGULAR;
+    if (fl.regularised) flags |= AOC_ST_REGULARISED;
+    return flags;
+}
+
 template <bool DIAG, typename XT>
 __global__ __launch_bounds__(TILE) void k_track_gains(KConst k, const XT* __restrict__ x,
                                                       const real* __restrict__ u, const real* __restrict__ x_opt0,
@@ -30,17 +55,7 @@ __global__ __launch_bounds__(TILE) void k_track_gains(KConst k, const XT* __rest
         const SC s = trig(xs[3], xs[5]);
         Lin l = linearise(k, xs, u0, s);
         track_lin_fields(l, [](int, real& v) { bw_opaque(v); });   // same cut as k_track_gains2, same roundings
-        real zz = R(0.0);
-        bw_opaque(zz);   // a run-time zero: both gain kernels then compile the same arithmetic for the affine terms
-        const real z6[6] = {zz, zz, zz, zz, zz, zz}, z2[2] = {zz, zz};
-        const StageFlags fl = lqr_stage(k, l, P, p, Qb, zz, zz, zz, z6, z2, [&](int c, real a, real b) {
-            if (c >= 1) {   // no feed-forward column here (q = r = 0)
-                Kout[tix<12>(tile, T, t, c - 1, lane)] = a;
-                Kout[tix<12>(tile, T, t, 5 + c, lane)] = b;
-            }
-        });
-        if (fl.singular) flags |= AOC_ST_SINGULAR;
-        if (fl.regularised) flags |= AOC_ST_REGULARISED;
+        flags |= track_gain_stage(k, l, P, p, Qb, Kout, tile, T, t, lane);
     }
 #pragma unroll
     for (int j = 0; j < 12; j++) Kout[tix<12>(tile, T, T - 1, j, lane)] = R(0.0);  // KK[:,:,T-1] stays 0 (:700)
@@ -110,17 +125,7 @@ __global__ __launch_bounds__(2 * TILE) void k_track_gains2(KConst kc, const XT* 
             Lin l;
             real(*src)[TILE][2] = sh[(j - 1) & 1];
             track_lin_fields(l, [&](int f, real& v) { v = src[f >> 1][lane][f & 1]; });
-            real zz = R(0.0);
-            bw_opaque(zz);
-            const real z6[6] = {zz, zz, zz, zz, zz, zz}, z2[2] = {zz, zz};
-            const StageFlags fl = lqr_stage(k, l, P, p, Qb, zz, zz, zz, z6, z2, [&](int c, real a, real b) {
-                if (c >= 1) {
-                    Kout[tix<12>(tile, T, tc, c - 1, lane)] = a;
-                    Kout[tix<12>(tile, T, tc, 5 + c, lane)] = b;
-                }
-            });
-            if (fl.singular) flags |= AOC_ST_SINGULAR;
-            if (fl.regularised) flags |= AOC_ST_REGULARISED;
+            flags |= track_gain_stage(k, l, P, p, Qb, Kout, tile, T, tc, lane);
           }
           __syncthreads();
         }
@@ -200,8 +205,7 @@ __global__ __launch_bounds__(4 * TILE) void k_track_gains4(KConst kc, const XT* 
             real(*srcP)[TILE][2] = shP[(j - 1) & 1];
             real(*dstP)[TILE][2] = shP[j & 1];
             track_lin_fields(l, [&](int f, real& v) { v = src[f >> 1][lane][f & 1]; });
-            real zz = R(0.0);
-            bw_opaque(zz);   // the run-time zero of k_track_gains: the same arithmetic in every gain kernel
+            const real zz = track_zero();   // the same arithmetic in every gain kernel
             const real z6[6] = {zz, zz, zz, zz, zz, zz}, z2[2] = {zz, zz};
             real Pn[21];
             StageFlags fl;
