@@ -241,6 +241,13 @@ __device__ __forceinline__ double div_r(double a, double b) { return a / b; }
 __device__ __forceinline__ float div_r(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
 #pragma clang fp contract(off)
+// The inputs of a trial or of the update, u' = u + a du (optcon.py:197 / :253): one product, one sum, two roundings
+// each.  Every rollout, every stored candidate and the copying update form them HERE, so that they agree bit for bit.
+__device__ __forceinline__ void step_inputs(real uc0, real uc1, real a, real d0, real d1, real& u0, real& u1) {
+    u0 = uc0 + a * d0;
+    u1 = uc1 + a * d1;
+}
+
 __device__ __forceinline__ void step_state(const KConst& k, const real x[6], real u0, real u1,
                                            const SC& s, real xp[6]) {
     const real V = x[2], al = x[3] - x[5];

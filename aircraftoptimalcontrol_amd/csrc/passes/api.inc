@@ -253,6 +253,11 @@ static int api_forward(const aoc_problem* p, const aoc_params* prm, int32_t n_sp
         else if (xrc) LAUNCH_FW_(N, true, float);                                                                   \
         else LAUNCH_FW_(N, false, float);                                                                           \
     } while (0))
+    // the role kernels of small batches (k_forward_split, _lin, _duo) take the same arguments: GROUPS workgroups per tile of
+    // NWAVES wavefronts
+#define LAUNCH_FW_ROLES(KERNEL, GROUPS, NWAVES)                                                                      \
+    hipLaunchKernelGGL(KERNEL, dim3(k.ntiles, GROUPS), dim3((NWAVES) * TILE), 0, st, k, *prm, n_spec, cb,           \
+                       (const real*)p->ref, (const XT*)x, u, x0, Kt, du, descent, J_trial, status, ntrials_hint)
     // the states are re-computed instead of read when the caller says they are the rollout of u (float32 storage only)
     const bool xrc = p->x_is_rollout && p->x_in_f32 && tuning().fw_recompute != 0;
     // small batches: one wavefront per chain, see k_forward_split
@@ -276,31 +281,21 @@ static int api_forward(const aoc_problem* p, const aoc_params* prm, int32_t n_sp
         const int duo_max = tuning().fw_duo == 1 ? 256 : tuning().fw_duo;   // workgroups the launch may have (1: one per CU)
         if (duo_max > 0 && n_spec > FWS_TPG && k.ntiles * ((n_spec + 1) / 2) <= duo_max) {
             AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT,
-#ifdef AOC_FWD_SINGLE
-                hipLaunchKernelGGL((k_forward_duo<D, RP, XT>), dim3(k.ntiles, n_spec), dim3(8 * TILE), 0, st, k, *prm, n_spec, cb,
-#else
-                hipLaunchKernelGGL((k_forward_duo<D, RP, XT>), dim3(k.ntiles, (n_spec + 1) / 2), dim3(8 * TILE), 0, st, k, *prm, n_spec, cb,
-#endif
-                                   (const real*)p->ref, (const XT*)x, u, x0, Kt, du, descent, J_trial, status, ntrials_hint)));
-            return check_launch("k_forward");
-        }
-        if (fw_lin > 0 || (fw_lin < 0 && n_spec <= FWL_TPG)) {
+                LAUNCH_FW_ROLES((k_forward_duo<D, RP, XT>), (n_spec + FWD_CPG - 1) / FWD_CPG, 8)));
+        } else if (fw_lin > 0 || (fw_lin < 0 && n_spec <= FWL_TPG)) {
             const int ngroups = (n_spec + FWL_TPG - 1) / FWL_TPG;
             AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT, AOC_DISPATCH_WPE(k.ntiles * ngroups <= one_per_cu, WPE,
-                hipLaunchKernelGGL((k_forward_lin<D, RP, XT, WPE>), dim3(k.ntiles, ngroups), dim3((2 + FWL_TPG) * TILE), 0, st, k, *prm,
-                                   n_spec, cb, (const real*)p->ref, (const XT*)x, u, x0, Kt, du, descent, J_trial, status,
-                                   ntrials_hint))));
-            return check_launch("k_forward");
+                LAUNCH_FW_ROLES((k_forward_lin<D, RP, XT, WPE>), ngroups, 2 + FWL_TPG))));
+        } else {
+            const int ngroups = (n_spec + FWS_TPG - 1) / FWS_TPG;
+            const int nwaves = 1 + (n_spec < FWS_TPG ? n_spec : FWS_TPG);
+            AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT, AOC_DISPATCH_WPE(k.ntiles * ngroups <= one_per_cu, WPE,
+                LAUNCH_FW_ROLES((k_forward_split<D, RP, XT, WPE>), ngroups, nwaves))));
         }
-        const int ngroups = (n_spec + FWS_TPG - 1) / FWS_TPG;
-        const int nwaves = 1 + (n_spec < FWS_TPG ? n_spec : FWS_TPG);
-        AOC_DISPATCH_DR(k, D, RP, AOC_DISPATCH_XT(p->x_in_f32, XT, AOC_DISPATCH_WPE(k.ntiles * ngroups <= one_per_cu, WPE,
-            hipLaunchKernelGGL((k_forward_split<D, RP, XT, WPE>), dim3(k.ntiles, ngroups), dim3(nwaves * TILE), 0, st, k, *prm,
-                               n_spec, cb, (const real*)p->ref, (const XT*)x, u, x0, Kt, du, descent, J_trial, status,
-                               ntrials_hint))));
     } else if (n_spec == 1) LAUNCH_FW(1);
     else if (n_spec == 2) LAUNCH_FW(2);
     else LAUNCH_FW(3);
+#undef LAUNCH_FW_ROLES
 #undef LAUNCH_FW
 #undef LAUNCH_FW_
     return check_launch("k_forward");

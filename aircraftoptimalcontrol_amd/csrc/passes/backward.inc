@@ -25,7 +25,9 @@ struct BwIn {
 // expressions of hessian() round identically) — so they do not travel: two doubles fewer alive across the cut, in LDS
 // and in the registers of the one-wavefront kernel, whose full-Hessian variant needs every register it can get.
 
-// the twelve state-dependent entries of the Jacobians, as they travel between wavefronts
+// the twelve state-dependent entries of the Jacobians, as they travel between wavefronts (TRACK_LIN_NF: how many, one more
+// than the largest index below — whoever sizes a record by it follows a field added here)
+constexpr int TRACK_LIN_NF = 12;
 template <typename F>
 __device__ __forceinline__ void track_lin_fields(Lin& l, F f) {
     f(0, l.a02); f(1, l.a05); f(2, l.a12); f(3, l.a15); f(4, l.a22); f(5, l.a23); f(6, l.a25);

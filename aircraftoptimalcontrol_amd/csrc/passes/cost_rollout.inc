@@ -79,11 +79,7 @@ __device__ __forceinline__ real rollout(const KConst& k, const real* __restrict_
                 }
             }
             real u0, u1;
-            {
-#pragma clang fp contract(off)
-                u0 = uc0 + a * dc0;  // optcon.py:197 / :253
-                u1 = uc1 + a * dc1;
-            }
+            step_inputs(uc0, uc1, a, dc0, dc1, u0, u1);
             JJ += stage_cost2<DIAG>(k, xs, u0, u1, ref_row<RPT>(k, ref, tile, lane, t, rb), q, r);
             if (WRITE && !(xs[2] > R(0.0))) flags |= AOC_ST_VNONPOS;  // trials are silent: only the update reports
             const SC s = trig(xs[3], xs[5]);

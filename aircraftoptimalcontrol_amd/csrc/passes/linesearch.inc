@@ -417,11 +417,7 @@ __device__ __forceinline__ void rollout_multi(const KConst& k, const real* __res
 #pragma unroll
             for (int j = 0; j < CPL; j++) {
                 real u0, u1, xn[6];
-                {
-#pragma clang fp contract(off)
-                    u0 = uc0 + a[j] * dc0;  // optcon.py:253
-                    u1 = uc1 + a[j] * dc1;
-                }
+                step_inputs(uc0, uc1, a[j], dc0, dc1, u0, u1);
                 JJ[j] += stage_cost2<DIAG>(k, xs[j], u0, u1, rr, q, r);
                 const SC s = trig(xs[j][3], xs[j][5], tk);
                 step_state(k, xs[j], u0, u1, s, xn);
@@ -573,11 +569,7 @@ __device__ __forceinline__ real rollout_split(const KConst& k, const real* __res
                 }
                 if (t < T - 1) {
                     real u0, u1;
-                    {
-#pragma clang fp contract(off)
-                        u0 = uc0 + a * dc0;  // optcon.py:197 / :253
-                        u1 = uc1 + a * dc1;
-                    }
+                    step_inputs(uc0, uc1, a, dc0, dc1, u0, u1);
                     dst[3][ll][0] = u0; dst[3][ll][1] = u1;
                     const SC s = trig(xs[3], xs[5], tk);
                     step_state(k, xs, u0, u1, s, xn);
@@ -659,11 +651,7 @@ __global__ __launch_bounds__(2 * TILE) void k_ls_final_split(KConst kc, int maxi
 #pragma unroll
                     for (int h = 0; h < 3; h++) v[h] = crec[((size_t)t * 3 + h) * TILE];
                     real u0, u1;
-                    {
-#pragma clang fp contract(off)
-                        u0 = uc0 + al * d0;
-                        u1 = uc1 + al * d1;
-                    }
+                    step_inputs(uc0, uc1, al, d0, d1, u0, u1);
                     u_new[tix<2>(tile, T, t, 0, lane)] = u0;
                     u_new[tix<2>(tile, T, t, 1, lane)] = u1;
 #pragma unroll

@@ -776,27 +776,38 @@ def test_forward_pass_with_a_linearisation_wavefront_changes_nothing(aoc, tuned)
     counts, costs, descents and status flags must equal those of k_forward_split bit for bit — with 2, 3, 7 and all 10
     candidates riding along (1 to 5 workgroups per tile, spare trial wavefronts, candidate stores with and without a
     hint), on a ragged batch, across the Hessian switch, for an even and an odd number of stages and for a
-    caller-supplied fp64 initial iterate."""
+    caller-supplied fp64 initial iterate; and for horizons shorter than its load rings (6 and 4 stages) and its hand-off
+    blocks (2 stages), down to T = 3."""
     from aircraftoptimalcontrol_amd import problems
+    prm = aoc.make_params(stepsize_0=1.0, armijo_maxiters=10)
+
+    def both(bp, T, B, x0, n_it, ns):
+        res = []
+        for lin in (0, 1):
+            tuned(nspec=ns, fw_lin=lin, fw_duo=0)
+            s = aoc.NewtonBatchSolver(bp, B, prm)
+            s.set_initial_from_x0(x0)
+            res.append((s.run_fixed(n_it), s.current(), s.direction()))
+        (ha, (xa, ua), da), (hb, (xb, ub), db) = res
+        assert np.array_equal(xa, xb, equal_nan=True) and np.array_equal(ua, ub, equal_nan=True), (T, ns)
+        assert np.array_equal(da, db, equal_nan=True), (T, ns)
+        for a, b in zip(ha, hb):
+            for key in a:
+                assert np.array_equal(a[key], b[key], equal_nan=True), (T, ns, key)
+
     for T, B in ((500, 200), (333, 70)):
         pr = problems.step_maneuver(1.0, 1.0 / T)
         assert pr.T == T
         bp = aoc.BatchProblem(pr.QQt, pr.RRt, pr.QQT, pr.xx_ref, pr.uu_ref, pr.dt)
         x0 = problems.random_x0(B, seed=23)
-        prm = aoc.make_params(stepsize_0=1.0, armijo_maxiters=10)
         for ns in (2, 3, 7, 10):
-            res = []
-            for lin in (0, 1):
-                tuned(nspec=ns, fw_lin=lin, fw_duo=0)
-                s = aoc.NewtonBatchSolver(bp, B, prm)
-                s.set_initial_from_x0(x0)
-                res.append((s.run_fixed(11 if ns == 10 else 4), s.current(), s.direction()))
-            (ha, (xa, ua), da), (hb, (xb, ub), db) = res
-            assert np.array_equal(xa, xb, equal_nan=True) and np.array_equal(ua, ub, equal_nan=True), (T, ns)
-            assert np.array_equal(da, db, equal_nan=True), (T, ns)
-            for a, b in zip(ha, hb):
-                for key in a:
-                    assert np.array_equal(a[key], b[key], equal_nan=True), (T, ns, key)
+            both(bp, T, B, x0, 11 if ns == 10 else 4, ns)
+    # horizons shorter than the load rings and the hand-off blocks
+    pr = problems.step_maneuver(1.0, 2e-3)
+    for T in (3, 4, 5, 6, 7, 9):
+        bp = aoc.BatchProblem(pr.QQt, pr.RRt, pr.QQT, pr.xx_ref[:, :T], pr.uu_ref[:, :T], pr.dt)
+        for ns in (2, 7):
+            both(bp, T, 70, problems.perturbed_x0(pr, 70, seed=T), 3, ns)
     # a caller-supplied iterate with arbitrary fp64 samples is read as fp64 by the first iteration
     g = load_golden("g6_chain_step_T500")
     pg = load_golden("problem_step_T500")
@@ -914,6 +925,36 @@ def test_forward_state_recomputation_does_not_change_results(aoc, tuned):
         r = orc.newton_iterate(op, orc.params(), 0, xi2[b], ui[b], xi2[b][:, 0])
         assert r["stepsize"] == sc["stepsize"][b] and abs(r["descent"] - sc["descent"][b]) <= 1e-8 * abs(r["descent"])
         assert rel_err(un[b], r["uu"], 1e-3) < 1e-8
+
+
+def test_forward_kernel_of_large_batches_at_tiny_horizons(aoc, tuned):
+    """k_forward at horizons shorter than or as long as its load ring (2 stages): 1, 2 and 3 candidates riding along, the
+    nominal states read and re-computed — six instantiations of one kernel whose iterates, directions, steps, trial counts,
+    costs, descents and status flags must be bit-identical to each other over 3 fixed iterations."""
+    from aircraftoptimalcontrol_amd import problems
+    pr = problems.step_maneuver(1.0, 2e-3)
+    prm = aoc.make_params(stepsize_0=1.0, armijo_maxiters=10)
+    B = 70
+    for T in (3, 4, 5):
+        bp = aoc.BatchProblem(pr.QQt, pr.RRt, pr.QQT, pr.xx_ref[:, :T], pr.uu_ref[:, :T], pr.dt)
+        x0 = problems.perturbed_x0(pr, B, seed=T)
+        res = {}
+        for ns in (1, 2, 3):
+            for rc in (0, 1):
+                tuned(nspec=ns, split_tiles=0, split_bw_tiles=0, fw_recompute=rc)
+                s = aoc.NewtonBatchSolver(bp, B, prm)
+                s.set_initial_from_x0(x0)
+                # the re-computing instantiation needs a rollout the library wrote AND float32 state storage
+                assert s.cur_rollout and not s.cur_is64 and s._xin()[1] == 1 and s.n_spec == ns
+                res[ns, rc] = (s.run_fixed(3), s.current(), s.direction())
+                assert s.cur_rollout and not s.cur_is64
+        ha, (xa, ua), da = res[1, 0]
+        for case, (hb, (xb, ub), db) in res.items():
+            assert np.array_equal(xa, xb, equal_nan=True) and np.array_equal(ua, ub, equal_nan=True), (T, case)
+            assert np.array_equal(da, db, equal_nan=True), (T, case)
+            for a, b in zip(ha, hb):
+                for key in a:
+                    assert np.array_equal(a[key], b[key], equal_nan=True), (T, case, key)
 
 
 def test_stored_candidates_do_not_change_results(aoc, tuned):
