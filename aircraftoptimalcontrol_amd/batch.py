@@ -983,6 +983,8 @@ ENS_REC = 20                       # doubles per stage record of `nominal`
 ENS_NSTAT = _lib.AOC_ENS_NSTAT     # statistics per member
 ENS_QUANTILES = (0.5, 0.9, 0.99)
 ENV_NREC = _lib.AOC_ENV_NREC       # doubles per (optimum, sample) record of aoc_track_ensemble_envelope
+HIST_NCH = _lib.AOC_HIST_NCH       # channels of aoc_track_ensemble_histogram: dx[0..5], du[0..1]
+HIST_NBIN = _lib.AOC_HIST_NBIN     # bins per (optimum, sample, channel)
 # the record (include/aoc.h): n | min dx | max dx | min du | max du | sum dx | sum dx_i dx_j (upper triangle, row by row)
 _ENV_MIN = np.r_[1:7, 13:15]
 _ENV_MAX = np.r_[7:13, 15:17]
@@ -1071,6 +1073,68 @@ def _envelope_dict(raw):
                 max_du=raw[:, 15:17].T.copy(), mean_dx=mean, cov_dx=cov, raw=raw)
 
 
+def histogram_bins(envelope_raw, pad=0.0):
+    """Equal bins over what the envelope saw: records (n_opt,T,44) (or (T,44)) -> bins (n_opt,T,8,2) = (lo, inv_w) per
+    optimum, sample and channel (dx[0..5], du[0..1]), the `bins` of aoc_track_ensemble_histogram: lo = min, inv_w =
+    64 / (max - min), the range widened by pad * (max - min) on either side first.  Where max == min the bins are
+    (that value, 0), where n = 0 (min / max infinite; du at sample T-1) they are (0, 0): everything then goes to bin 0.
+    NumPy only, needs no GPU."""
+    raw = np.asarray(envelope_raw, dtype=np.float64)
+    raw = raw[None] if raw.ndim == 2 else raw
+    if raw.ndim != 3 or raw.shape[2] != ENV_NREC:
+        raise ValueError("records (n_opt, T, %d) expected, got %s" % (ENV_NREC, raw.shape))
+    mn, mx = raw[..., _ENV_MIN], raw[..., _ENV_MAX]
+    some = np.isfinite(mn) & np.isfinite(mx)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        span = np.where(some, mx - mn, 0.0)
+        lo = np.where(some, mn - pad * span, 0.0)
+        w = span * (1.0 + 2.0 * pad)
+        inv_w = np.where(some & (w > 0) & np.isfinite(w), HIST_NBIN / w, 0.0)
+    inv_w = np.where(np.isfinite(inv_w), inv_w, 0.0)          # a range so narrow that 64 / w overflows: one value
+    return np.ascontiguousarray(np.stack([lo, inv_w], axis=-1))
+
+
+def histogram_merge(a, b):
+    """Counts (..., 8, 64) of two disjoint sets of members under the SAME bins -> the counts of their union: addition.
+    What joins calls cut by `first=`, shards and devices.  NumPy only, needs no GPU."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.shape[-2:] != (HIST_NCH, HIST_NBIN) or a.dtype.kind not in "iu" or b.dtype.kind not in "iu":
+        raise ValueError("two integer arrays of counts (..., %d, %d) of one shape expected, got %s %s %s %s"
+                         % (HIST_NCH, HIST_NBIN, a.shape, a.dtype, b.shape, b.dtype))
+    return a.astype(np.int64) + b.astype(np.int64)
+
+
+def histogram_quantiles(hist, bins, q):
+    """Quantile tubes from counts: hist (n_opt,T,8,64) (or (T,8,64)), bins (n_opt,T,8,2) (or (T,8,2)), q a sequence of
+    levels in [0,1] -> tube (len(q),n_opt,8,T), width (n_opt,8,T).  With n the sum of the counts of (optimum, sample,
+    channel) and r = max(1, ceil(q n)), the value is the midpoint lo + (k + 0.5) / inv_w of the first bin k whose
+    cumulative count reaches r (lo where inv_w = 0), NaN where n = 0; width = 1 / inv_w (0 where inv_w = 0) is the
+    resolution: where nothing fell outside the bins, the r-th order statistic lies in bin k, within width / 2 of the
+    value.  NumPy only, needs no GPU."""
+    h, b = np.asarray(hist), np.asarray(bins, dtype=np.float64)
+    if h.ndim == 3:
+        h, b = h[None], (b[None] if b.ndim == 3 else b)
+    if h.ndim != 4 or h.shape[2:] != (HIST_NCH, HIST_NBIN) or b.shape != h.shape[:3] + (2,):
+        raise ValueError("hist (n_opt,T,%d,%d) and bins (n_opt,T,%d,2) expected, got %s %s"
+                         % (HIST_NCH, HIST_NBIN, HIST_NCH, h.shape, b.shape))
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if q.ndim != 1 or not np.all((q >= 0) & (q <= 1)):
+        raise ValueError("quantile levels in [0, 1] expected, got %s" % (q,))
+    cum = np.cumsum(h.astype(np.int64), axis=-1)                                  # (n_opt,T,8,64)
+    n = cum[..., -1]
+    lo, inv_w = b[..., 0], b[..., 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        width = np.where(inv_w != 0, 1.0 / inv_w, 0.0)
+    tube = np.empty((q.size,) + n.shape)
+    for i, f in enumerate(q):
+        r = np.maximum(1, np.ceil(f * n)).astype(np.int64)
+        k = (cum < r[..., None]).sum(axis=-1)                                     # first bin whose cumulative count reaches r
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mid = np.where(inv_w != 0, lo + (k + 0.5) / inv_w, lo)
+        tube[i] = np.where(n > 0, mid, np.nan)
+    return np.ascontiguousarray(tube.transpose(0, 1, 3, 2)), np.ascontiguousarray(width.transpose(0, 2, 1))
+
+
 def _ens_summary(torch, v):
     """mean / max / quantiles over the members (rows) of one optimum, reduced on the device"""
     q = torch.quantile(v, torch.tensor(ENS_QUANTILES, dtype=v.dtype, device=v.device), dim=0)
@@ -1080,7 +1144,8 @@ def _ens_summary(torch, v):
 
 
 def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, sigma=None, seed=20260405, first=0,
-                   step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True, envelope=False):
+                   step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True, envelope=False,
+                   quantiles=None, bins=None):
     """Closed-loop tracking ensemble about shared optima (aoc_track_ensemble): the loop of lqr_tracking.py:279-281 for B
     members, u_t = u_opt_t + K_t (x_t - x_opt_t), x_{t+1} = step(x_t, u_t) + d_t, reduced to per-member statistics on
     the device; the optimum and its gains are stored once per optimum, not once per member.
@@ -1098,7 +1163,15 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     envelope=True (aoc_track_ensemble_envelope; every other output keeps its bits): also `envelope`, per optimum the
     reduction over its members at every sample, dict(n (T,) int = members still in the domain, min_dx / max_dx (6,T),
     min_du / max_du (2,T; sample T-1: +inf / -inf), mean_dx (6,T), cov_dx (6,6,T) (population covariance; NaN where
-    n = 0), raw (T,44) = the device's record, see envelope_merge / envelope_moments)."""
+    n = 0), raw (T,44) = the device's record, see envelope_merge / envelope_moments).
+    quantiles=(0.05, 0.5, 0.95) (aoc_track_ensemble_histogram; every other output keeps its bits): quantile tubes over the
+    members at every sample, from a 64-bin histogram per (optimum, sample, channel dx[0..5], du[0..1]) counted on the
+    device.  bins=None: two passes over the same members — the envelope call first (`envelope` is returned as above),
+    histogram_bins of its min / max, then the histogram call, which bins exactly the values the first pass saw; bins
+    (n_opt,T,8,2) (or (T,8,2)) = (lo, inv_w): the caller's own — fixed corridors, or the common bins of a sharded job,
+    whose counts histogram_merge adds — and no envelope call (unless envelope=True asks for it).  Adds, each a list per
+    optimum: hist (T,8,64) int32, bins (T,8,2), tube (len(quantiles),8,T) and tube_width (8,T) (histogram_quantiles:
+    bin midpoints and the bin width, the resolution), and `quantiles` as given."""
     torch = _torch()
     dev = problem.device
     xo, uo = np.asarray(xx_opt, dtype=np.float64), np.asarray(uu_opt, dtype=np.float64)
@@ -1134,6 +1207,18 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
         nz = _lib.MpcNoise(int(seed), int(step0), int(first), (C.c_double * 6)(*np.asarray(sigma, dtype=np.float64).tolist()))
     p = problem.c_problem(B, x_out_f32=int(bool(f32)))
     nzp = C.byref(nz) if nz is not None else None
+    hist = quantiles is not None
+    if hist:
+        quantiles = tuple(float(f) for f in np.atleast_1d(np.asarray(quantiles, dtype=np.float64)))
+        if bins is not None:
+            bins = np.asarray(bins, dtype=np.float64)
+            bins = bins[None] if bins.ndim == 3 else bins
+            if bins.shape != (n_opt, T, HIST_NCH, 2):
+                raise ValueError("bins must be (n_opt,T,%d,2) = %s, got %s" % (HIST_NCH, (n_opt, T, HIST_NCH, 2), bins.shape))
+        else:
+            envelope = True
+    elif bins is not None:
+        raise ValueError("bins= goes with quantiles=")
     if envelope:
         env = torch.empty((n_opt, T, ENV_NREC), dtype=torch.float64, device=dev)
         nbytes = int(lib().aoc_ensemble_envelope_scratch_bytes(B, T, mpo))
@@ -1141,7 +1226,27 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
         check(lib().aoc_track_ensemble_envelope(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp, _ptr(xr), _ptr(ur),
                                                 _ptr(ds), _ptr(stats), _ptr(status), _ptr(env), _ptr(scratch), nbytes),
               "aoc_track_ensemble_envelope")
-    else:
+        # the 352 B per tile and sample go back before the histogram's 512 B are taken; the kernels run on the stream of
+        # the caching allocator that frees them, so a later owner of the memory is ordered behind them
+        del scratch
+    if hist:
+        # the second pass over the same members: with the envelope's call before it, it repeats the statistics only (same
+        # bits, into buffers of its own); with the caller's bins it is the one call and writes everything
+        if bins is None:
+            bins = histogram_bins(env.cpu().numpy())
+        bins_d = torch.from_numpy(np.ascontiguousarray(bins)).to(dev)
+        hist_d = torch.empty((n_opt, T, HIST_NCH, HIST_NBIN), dtype=torch.int32, device=dev)
+        nbytes = int(lib().aoc_ensemble_histogram_scratch_bytes(B, T, mpo))
+        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+        first_call = not envelope
+        h_stats, h_status = (stats, status) if first_call else (torch.empty_like(stats), torch.zeros_like(status))
+        h_out = (xr, ur, ds) if first_call else (None, None, None)
+        check(lib().aoc_track_ensemble_histogram(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp, _ptr(bins_d),
+                                                 _ptr(h_out[0]), _ptr(h_out[1]), _ptr(h_out[2]), _ptr(h_stats), _ptr(h_status),
+                                                 _ptr(hist_d), _ptr(scratch) if nbytes else None, nbytes),
+              "aoc_track_ensemble_histogram")
+        del scratch
+    if not envelope and not hist:
         check(lib().aoc_track_ensemble(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp,
                                        _ptr(xr), _ptr(ur), _ptr(ds), _ptr(stats), _ptr(status)), "aoc_track_ensemble")
     sv = unpack_vec(stats, B)                                   # (B,16) on the device
@@ -1157,6 +1262,11 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
                status=status[:B].cpu().numpy(), stats=s, members_per_opt=mpo, group=group, summary=summary)
     if envelope:
         out["envelope"] = [_envelope_dict(r) for r in env.cpu().numpy()]
+    if hist:
+        counts = hist_d.cpu().numpy()
+        tube, width = histogram_quantiles(counts, bins, quantiles)
+        out.update(quantiles=quantiles, hist=list(counts), bins=list(bins), tube=list(tube.transpose(1, 0, 2, 3)),
+                   tube_width=list(width))
     if trajectories:
         xd = unpack(xr, B)
         xd[:, :, 0] = _dev_f64(x0, dev)                         # sample 0 is the fp64 x0, as everywhere

@@ -513,8 +513,8 @@ int aoc_track_ensemble(const aoc_problem* p, int32_t n_opt, int32_t members_per_
                        const double* x0_reg, const aoc_mpc_noise* noise, void* x_reg, double* u_reg, double* dist_out,
                        double* stats, int32_t* status) {
     static_assert(aoc64::ENS_NSTAT == AOC_ENS_NSTAT, "stats rows of the kernel and of the header");
-    return aoc64::api_track_ensemble("aoc_track_ensemble", false, p, n_opt, members_per_opt, nominal, x0_reg, noise, x_reg, u_reg,
-                                     dist_out, stats, status, nullptr, nullptr, 0);
+    return aoc64::api_track_ensemble("aoc_track_ensemble", aoc64::ENS_PLAIN, p, n_opt, members_per_opt, nominal, x0_reg, noise,
+                                     x_reg, u_reg, dist_out, stats, status, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
 size_t aoc_ensemble_envelope_scratch_bytes(int32_t B, int32_t T, int32_t members_per_opt) {
@@ -525,8 +525,21 @@ int aoc_track_ensemble_envelope(const aoc_problem* p, int32_t n_opt, int32_t mem
                                 const double* x0_reg, const aoc_mpc_noise* noise, void* x_reg, double* u_reg, double* dist_out,
                                 double* stats, int32_t* status, double* envelope, void* scratch, size_t scratch_bytes) {
     static_assert(aoc64::ENV_NREC == AOC_ENV_NREC, "envelope record of the kernel and of the header");
-    return aoc64::api_track_ensemble("aoc_track_ensemble_envelope", true, p, n_opt, members_per_opt, nominal, x0_reg, noise, x_reg,
-                                     u_reg, dist_out, stats, status, envelope, scratch, scratch_bytes);
+    return aoc64::api_track_ensemble("aoc_track_ensemble_envelope", aoc64::ENS_ENVELOPE, p, n_opt, members_per_opt, nominal, x0_reg,
+                                     noise, x_reg, u_reg, dist_out, stats, status, envelope, nullptr, nullptr, scratch, scratch_bytes);
+}
+
+size_t aoc_ensemble_histogram_scratch_bytes(int32_t B, int32_t T, int32_t members_per_opt) {
+    return aoc64::ensemble_histogram_scratch_bytes(B, T, members_per_opt);
+}
+
+int aoc_track_ensemble_histogram(const aoc_problem* p, int32_t n_opt, int32_t members_per_opt, const double* nominal,
+                                 const double* x0_reg, const aoc_mpc_noise* noise, const double* bins, void* x_reg, double* u_reg,
+                                 double* dist_out, double* stats, int32_t* status, int32_t* hist, void* scratch,
+                                 size_t scratch_bytes) {
+    static_assert(aoc64::HIST_NCH == AOC_HIST_NCH && aoc64::HIST_NBIN == AOC_HIST_NBIN, "histogram of the kernel and of the header");
+    return aoc64::api_track_ensemble("aoc_track_ensemble_histogram", aoc64::ENS_HISTOGRAM, p, n_opt, members_per_opt, nominal, x0_reg,
+                                     noise, x_reg, u_reg, dist_out, stats, status, nullptr, bins, hist, scratch, scratch_bytes);
 }
 
 // ---- float32 arithmetic (aoc32): every array, the reference curves and the workspace are float32 ------

@@ -71,6 +71,27 @@ constexpr bool env_tasks_cover() {
 }
 static_assert(env_tasks_cover(), "the 14 tasks are the 28 sums of the record, each once");
 
+// ---- per-sample histogram over the members (aoc_track_ensemble_histogram) ---------------------------------------------
+// hist[opt][t][c][k], c = dx[0..5], du[0..1], k = bin of s = (v - lo) * inv_w under bins[opt][t][c] = (lo, inv_w)
+// (include/aoc.h).  The 16 doubles of a stage's bins travel like the nominal's record: HIST_PF coalesced doubles per lane
+// a block ahead into LDS, read back as eight ds_read_b128 at one address for all lanes (block b = the records
+// b*ENS_BLK .. of the SAME stages: bins are used where the stage starts, not a stage ahead).  A tile has 64 members, so a
+// count of a tile fits a byte: the HIST instances keep, per sample slot and channel, 64 byte counters as 16 dwords in LDS,
+// and a lane that counts adds 1 << 8 (k % 4) to dword k / 4 with one returnless ds_add_u32 — no carry can cross a byte
+// (at most 64 adds of 1 each).  The counters ARE the tile's partial part[tile][t][c][64 bytes]: every HIST_S samples the
+// wavefront copies them out as they lie, 16 bytes per lane and instruction (ds_read_b128 / global store / ds_write_b128 of
+// zeros, all conflict-free and coalesced), and k_histogram_fold adds the tiles of an optimum into int32.
+constexpr int HIST_NCH = 8;     // AOC_HIST_NCH
+constexpr int HIST_NBIN = 64;   // AOC_HIST_NBIN
+constexpr int HIST_REC = 2 * HIST_NCH;              // doubles per stage of `bins`
+constexpr int HIST_PF = ENS_BLK * HIST_REC / TILE;  // doubles per lane and block
+constexpr int HIST_S = 8;                           // samples between two drains
+constexpr int HIST_DW = HIST_NCH * HIST_NBIN / 4;   // dwords of byte counters per sample (and tile)
+constexpr int HIST_DRAIN = HIST_S * HIST_DW / 4 / TILE;   // 16-byte pieces per lane and drain
+static_assert(HIST_PF * TILE == ENS_BLK * HIST_REC, "a block of bins is a whole number of doubles per lane");
+static_assert(HIST_DRAIN * TILE * 4 == HIST_S * HIST_DW, "a drain is a whole number of 16-byte pieces per lane");
+static_assert(TILE <= 255, "a tile's count fits a byte");
+
 // max over |v| with a NaN that sticks (fmax would drop it): for non-negative doubles the IEEE order is the order of
 // the bit patterns as unsigned integers, and every NaN lies above +inf there
 __device__ __forceinline__ void ens_absmax(unsigned long long& m, double v) {
@@ -86,15 +107,20 @@ __device__ __forceinline__ bool ens_finite6(const real x[6]) {
 // WRITE: x_reg / u_reg / dist_out (each may still be NULL) are written; NOISE: d_t drawn by mpc_noise_draw with the counter
 // (first + member, step + t, c / 2, 0); the stats-only, noise-free instance carries neither stores nor the generator.
 // ENV: also the per-tile envelope records part[tile][t][ENV_NREC] (above); every other output keeps its bits.
-template <bool WRITE, bool NOISE, typename XO, bool DIAG, bool ENV = false>
+// HIST: also the per-tile byte counts part[tile][t][HIST_NCH][HIST_NBIN] under `bins` (above); never together with ENV.
+template <bool WRITE, bool NOISE, typename XO, bool DIAG, bool ENV = false, bool HIST = false>
 __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_per_opt, const real* __restrict__ nominal,
                                                          const real* __restrict__ x0, MpcNoise nz, XO* __restrict__ x_reg,
                                                          real* __restrict__ u_reg, real* __restrict__ dist_out,
                                                          real* __restrict__ stats, int* __restrict__ status,
-                                                         real* __restrict__ part = nullptr) {
+                                                         real* __restrict__ part = nullptr,
+                                                         const real* __restrict__ bins = nullptr) {
 #pragma clang fp contract(off)
+    static_assert(!(ENV && HIST), "the bins come from an envelope call: the two are never one instance");
     __shared__ __attribute__((aligned(16))) real sh[2][ENS_BLK * ENS_REC];
     __shared__ __attribute__((aligned(16))) real ev[ENV ? ENV_S * ENV_ROWS * ENV_LD : 2];
+    __shared__ __attribute__((aligned(16))) real hb[HIST ? 2 * ENS_BLK * HIST_REC : 2];
+    __shared__ __attribute__((aligned(16))) unsigned hc[HIST ? HIST_S * HIST_DW : 4];
     // uniform constants in VGPRs (aoc_device.h pin_consts) where the SGPRs do not hold them: the diagonal weights (dense
     // ones are re-loaded from the kernel arguments inside the stage), and beside the generator's constants the model too
     KConst k = kc;
@@ -105,7 +131,9 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
     int member = tile * TILE + lane;
     if (member >= k.B) member = k.B - 1;   // lanes beyond B replicate member B-1, its draws included
     const size_t nrec = (size_t)T * ENS_REC;
-    real xs[6], xn[6], cur[ENS_REC], q[6], r[2], pf[ENS_PF];
+    real xs[6], xn[6], cur[ENS_REC], q[6], r[2], pf[ENS_PF], hpf[HIST ? HIST_PF : 1];
+    const real* __restrict__ bin = HIST ? bins + (size_t)(tile / tiles_per_opt) * T * HIST_REC : nullptr;   // wave-uniform
+    const size_t nbin = (size_t)T * HIST_REC;
     // block b of the nominal = records b*ENS_BLK + 1 .. (b+1)*ENS_BLK (what the stages b*ENS_BLK .. read AHEAD), one
     // coalesced load of ENS_PF doubles per lane; indices beyond the last record are clamped onto it
     auto fetch = [&](int b) {
@@ -114,10 +142,21 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
             const size_t e = ((size_t)b * ENS_BLK + 1) * ENS_REC + i * TILE + lane;
             pf[i] = nom[e < nrec ? e : nrec - 1];
         }
+        if (HIST) {   // block b of the bins = records b*ENS_BLK .. (b+1)*ENS_BLK - 1, clamped likewise
+#pragma unroll
+            for (int i = 0; i < HIST_PF; i++) {
+                const size_t e = (size_t)b * ENS_BLK * HIST_REC + i * TILE + lane;
+                hpf[i] = bin[e < nbin ? e : nbin - 1];
+            }
+        }
     };
     auto stash = [&](int b) {
 #pragma unroll
         for (int i = 0; i < ENS_PF; i++) sh[b & 1][i * TILE + lane] = pf[i];
+        if (HIST) {
+#pragma unroll
+            for (int i = 0; i < HIST_PF; i++) hb[(b & 1) * ENS_BLK * HIST_REC + i * TILE + lane] = hpf[i];
+        }
         __syncthreads();   // one wavefront: orders the LDS writes before the broadcast reads, costs nothing
     };
     // envelope: what this lane reduces (fixed for the whole kernel) and where its results go
@@ -184,6 +223,41 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
         }
         __syncthreads();   // the rows are read before the next samples overwrite them
     };
+    // histogram: sample t of this member into slot t % HIST_S: one returnless LDS add per channel (nc of them: sample T-1
+    // has no input).  A member that does not count adds 0, wherever its (possibly NaN) values point.
+    auto hist_put = [&](int t, const real dx[6], real du0, real du1, bool counts, int nc) {
+        const real2v* __restrict__ lw = (const real2v*)&hb[((t / ENS_BLK) & 1) * ENS_BLK * HIST_REC + (t % ENS_BLK) * HIST_REC];
+        unsigned* __restrict__ slot = &hc[(t & (HIST_S - 1)) * HIST_DW];
+#pragma unroll
+        for (int c = 0; c < HIST_NCH; c++) {
+            if (c >= nc) break;
+            const real v = c < 6 ? dx[c] : (c == 6 ? du0 : du1);
+            const real2v b = lw[c];                       // (lo, inv_w): every lane the same address
+            const real d = v - b.x, s = d * b.y;          // two roundings (contraction is off)
+            const int k = s >= R(63.0) ? 63 : (s >= R(1.0) ? (int)s : 0);   // NaN: both comparisons fail, bin 0
+            __hip_atomic_fetch_add(&slot[c * (HIST_NBIN / 4) + (k >> 2)], counts ? 1u << ((k & 3) * 8) : 0u, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    };
+    // the samples tb .. tb + ns - 1 (slots 0 .. ns-1) of the tile go out as they lie, and the counters start again from 0
+    auto hist_drain = [&](int tb, int ns) {
+        __syncthreads();   // one wavefront: the adds have landed
+        uint4* __restrict__ po = (uint4*)((unsigned*)part + ((size_t)tile * T + tb) * HIST_DW);
+        uint4* __restrict__ pc = (uint4*)hc;
+#pragma unroll
+        for (int i = 0; i < HIST_DRAIN; i++) {
+            const int e = i * TILE + lane;                // 16-byte piece e: sample slot e / (HIST_DW / 4)
+            const uint4 v = pc[e];
+            if (e < ns * (HIST_DW / 4)) po[e] = v;
+            pc[e] = make_uint4(0u, 0u, 0u, 0u);
+        }
+        __syncthreads();   // cleared before the next samples add
+    };
+    if (HIST) {
+        uint4* __restrict__ pc = (uint4*)hc;
+#pragma unroll
+        for (int i = 0; i < HIST_DRAIN; i++) pc[i * TILE + lane] = make_uint4(0u, 0u, 0u, 0u);
+    }
     unsigned long long mx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     real JJ = R(0.0);
     int flags = 0, first_bad = T;
@@ -224,6 +298,10 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
         if (ENV) {
             env_put(t, d, u0 - cur[6], u1 - cur[7], in_B && first_bad > t);
             if ((t & (ENV_S - 1)) == ENV_S - 1) env_reduce(t - (ENV_S - 1), ENV_S);
+        }
+        if (HIST) {
+            hist_put(t, d, u0 - cur[6], u1 - cur[7], in_B && first_bad > t, HIST_NCH);
+            if ((t & (HIST_S - 1)) == HIST_S - 1) hist_drain(t - (HIST_S - 1), HIST_S);
         }
         JJ += stage_cost2<DIAG>(k, xs, u0, u1, cur, q, r);   // as k_traj_cost with ref = (x_opt, u_opt)
         // Everything that reads the record is above; the plant step below (three quarters of the stage) does not.  The
@@ -273,6 +351,10 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
         env_put(T - 1, dT, R(0.0), R(0.0), in_B && first_bad > T - 1);
         env_reduce((T - 1) & ~(ENV_S - 1), ((T - 1) & (ENV_S - 1)) + 1);
     }
+    if (HIST) {
+        hist_put(T - 1, dT, R(0.0), R(0.0), in_B && first_bad > T - 1, 6);
+        hist_drain((T - 1) & ~(HIST_S - 1), ((T - 1) & (HIST_S - 1)) + 1);
+    }
     JJ += term_cost2<DIAG>(k, xs, cur, q);
     if (WRITE && x_reg) {
         st_stream(&u_reg[tix<2>(tile, T, T - 1, 0, lane)], R(0.0));
@@ -320,6 +402,39 @@ __global__ __launch_bounds__(ENV_FOLD_THREADS) void k_envelope_fold(int n_opt, i
     envelope[idx] = acc;
 }
 
+// hist[opt][t][c][k] (int32) from part[tile][t][c][k] (bytes): the tiles of an optimum added up, one thread per dword of
+// the partial = four bins (coalesced dword loads, sixteen in flight; one 16-byte store).  Integers: any order gives the same.
+template <typename = void>
+__global__ __launch_bounds__(ENV_FOLD_THREADS) void k_histogram_fold(int n_opt, int T, int ntiles, int tiles_per_opt,
+                                                                     const unsigned* __restrict__ part, int* __restrict__ hist) {
+    const size_t per_opt = (size_t)T * HIST_DW, idx = (size_t)blockIdx.x * ENV_FOLD_THREADS + threadIdx.x;
+    if (idx >= (size_t)n_opt * per_opt) return;
+    const int opt = (int)(idx / per_opt);
+    const int first = opt * tiles_per_opt, last = first + tiles_per_opt < ntiles ? first + tiles_per_opt : ntiles;
+    const unsigned* __restrict__ src = part + (size_t)first * per_opt + (idx - (size_t)opt * per_opt);
+    // two bytes at a time in the halves of a dword: a group of sixteen tiles adds at most 16 * 64 to a half
+    int acc[4] = {0, 0, 0, 0};
+    int i = first;
+    for (; i + 16 <= last; i += 16) {
+        unsigned v[16], even = 0u, odd = 0u;
+#pragma unroll
+        for (int j = 0; j < 16; j++) v[j] = src[(size_t)j * per_opt];
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            even += v[j] & 0x00ff00ffu;
+            odd += (v[j] >> 8) & 0x00ff00ffu;
+        }
+        acc[0] += (int)(even & 0xffffu); acc[2] += (int)(even >> 16);
+        acc[1] += (int)(odd & 0xffffu);  acc[3] += (int)(odd >> 16);
+        src += 16 * per_opt;
+    }
+    for (; i < last; i++, src += per_opt) {
+        const unsigned v = *src;
+        acc[0] += (int)(v & 0xffu); acc[1] += (int)((v >> 8) & 0xffu); acc[2] += (int)((v >> 16) & 0xffu); acc[3] += (int)(v >> 24);
+    }
+    ((int4*)hist)[idx] = make_int4(acc[0], acc[1], acc[2], acc[3]);
+}
+
 #ifndef AOC_KERNELS_ONLY
 // aoc_ensemble_envelope_scratch_bytes: part[ntiles][T][ENV_NREC]; 0 for a geometry the call refuses anyway
 static size_t ensemble_envelope_scratch_bytes(int32_t B, int32_t T, int32_t members_per_opt) {
@@ -327,19 +442,31 @@ static size_t ensemble_envelope_scratch_bytes(int32_t B, int32_t T, int32_t memb
     return (size_t)((B + TILE - 1) / TILE) * (size_t)T * ENV_NREC * sizeof(double);
 }
 
-// Body of aoc_track_ensemble and (env: with envelope, scratch, scratch_bytes) of aoc_track_ensemble_envelope, fn the name
+// aoc_ensemble_histogram_scratch_bytes: part[ntiles][T][HIST_NCH][HIST_NBIN] bytes; 0 for a geometry the call refuses anyway
+static size_t ensemble_histogram_scratch_bytes(int32_t B, int32_t T, int32_t members_per_opt) {
+    if (B < 1 || T < 1 || members_per_opt < TILE || members_per_opt % TILE) return 0;
+    return (size_t)((B + TILE - 1) / TILE) * (size_t)T * HIST_DW * sizeof(unsigned);
+}
+
+enum { ENS_PLAIN = 0, ENS_ENVELOPE = 1, ENS_HISTOGRAM = 2 };
+
+// Body of aoc_track_ensemble, (mode ENS_ENVELOPE: with envelope, scratch, scratch_bytes) of aoc_track_ensemble_envelope and
+// (mode ENS_HISTOGRAM: with bins, hist, scratch, scratch_bytes) of aoc_track_ensemble_histogram, fn the name
 // of the entry point for the reasons.  A template only so that the kernels it names are instantiated where it is called
 // — from the fp64 entry points — and not once more in the float32 namespace.
 template <typename = void>
-static int api_track_ensemble(const char* fn, bool env, const aoc_problem* p, int32_t n_opt, int32_t members_per_opt,
+static int api_track_ensemble(const char* fn, int mode, const aoc_problem* p, int32_t n_opt, int32_t members_per_opt,
                               const real* nominal, const real* x0_reg, const aoc_mpc_noise* noise, void* x_reg, real* u_reg,
-                              real* dist_out, real* stats, int32_t* status, real* envelope, void* scratch,
-                              size_t scratch_bytes) {
+                              real* dist_out, real* stats, int32_t* status, real* envelope, const real* bins, int32_t* hist,
+                              void* scratch, size_t scratch_bytes) {
+    const bool env = mode == ENS_ENVELOPE, hst = mode == ENS_HISTOGRAM;
     if (!p) return einval("%s: aoc_problem is NULL", fn);
     if (!nominal) return einval("%s: nominal is NULL", fn);
     if (!x0_reg) return einval("%s: x0_reg is NULL", fn);
     if (!stats) return einval("%s: stats is NULL", fn);
     if (env && !envelope) return einval("%s: envelope is NULL", fn);
+    if (hst && !bins) return einval("%s: bins is NULL", fn);
+    if (hst && !hist) return einval("%s: hist is NULL", fn);
     if (n_opt < 1) return einval("%s: n_opt = %d (need n_opt >= 1)", fn, n_opt);
     if (members_per_opt < TILE || members_per_opt % TILE)
         return einval("%s: members_per_opt = %d is not a positive multiple of %d", fn, members_per_opt, TILE);
@@ -360,6 +487,14 @@ static int api_track_ensemble(const char* fn, bool env, const aoc_problem* p, in
         if (scratch_bytes < need)
             return einval("%s: scratch_bytes = %zu, need %zu (aoc_ensemble_envelope_scratch_bytes)", fn, scratch_bytes, need);
     }
+    if (hst) {
+        const size_t need = ensemble_histogram_scratch_bytes(p->B, p->T, members_per_opt);
+        if (!scratch) return einval("%s: scratch is NULL (need %zu bytes, aoc_ensemble_histogram_scratch_bytes)", fn, need);
+        if (scratch_bytes < need)
+            return einval("%s: scratch_bytes = %zu, need %zu (aoc_ensemble_histogram_scratch_bytes)", fn, scratch_bytes, need);
+        if ((uintptr_t)scratch % 16 || (uintptr_t)hist % 16)
+            return einval("%s: scratch and hist must be 16-byte aligned", fn);
+    }
     KConst k = make_const(p->model, p->QQt, p->RRt, p->QQT, p->B, p->T);
     MpcNoise nz;
     memset(&nz, 0, sizeof nz);
@@ -378,6 +513,9 @@ static int api_track_ensemble(const char* fn, bool env, const aoc_problem* p, in
 #define AOC_ENV_LAUNCH(W, N, XO, D)                                                                                      \
     hipLaunchKernelGGL((k_track_ensemble<W, N, XO, D, true>), dim3(k.ntiles), dim3(TILE), 0, st, k, tpo, nominal, x0_reg, \
                        nz, (XO*)x_reg, u_reg, dist_out, stats, status, (real*)scratch)
+#define AOC_HIST_LAUNCH(W, N, XO, D)                                                                                            \
+    hipLaunchKernelGGL((k_track_ensemble<W, N, XO, D, false, true>), dim3(k.ntiles), dim3(TILE), 0, st, k, tpo, nominal, x0_reg, \
+                       nz, (XO*)x_reg, u_reg, dist_out, stats, status, (real*)scratch, bins)
 #define AOC_ENS_DISPATCH(LAUNCH)                                                                                        \
     do {                                                                                                                \
         if (p->x_out_f32 && x_reg) /* (never with noise, see above) */                                                  \
@@ -385,8 +523,16 @@ static int api_track_ensemble(const char* fn, bool env, const aoc_problem* p, in
         else                                                                                                            \
             AOC_DISPATCH_BOOL(write, W, AOC_DISPATCH_BOOL(nz.on, N, AOC_DISPATCH_BOOL(k.diag, D, LAUNCH(W, N, double, D)))); \
     } while (0)
-    if (!env) {
+    if (mode == ENS_PLAIN) {
         AOC_ENS_DISPATCH(AOC_ENS_LAUNCH);
+        return check_launch(fn);
+    }
+    if (hst) {
+        AOC_ENS_DISPATCH(AOC_HIST_LAUNCH);
+        if (int rc = check_launch(fn)) return rc;
+        const size_t total = (size_t)n_opt * p->T * HIST_DW;
+        hipLaunchKernelGGL(k_histogram_fold<>, dim3((unsigned)((total + ENV_FOLD_THREADS - 1) / ENV_FOLD_THREADS)),
+                           dim3(ENV_FOLD_THREADS), 0, st, n_opt, p->T, k.ntiles, tpo, (const unsigned*)scratch, hist);
         return check_launch(fn);
     }
     AOC_ENS_DISPATCH(AOC_ENV_LAUNCH);
@@ -395,6 +541,7 @@ static int api_track_ensemble(const char* fn, bool env, const aoc_problem* p, in
     hipLaunchKernelGGL(k_envelope_fold<>, dim3((unsigned)((total + ENV_FOLD_THREADS - 1) / ENV_FOLD_THREADS)),
                        dim3(ENV_FOLD_THREADS), 0, st, n_opt, p->T, k.ntiles, tpo, (const real*)scratch, envelope);
 #undef AOC_ENS_DISPATCH
+#undef AOC_HIST_LAUNCH
 #undef AOC_ENV_LAUNCH
 #undef AOC_ENS_LAUNCH
     return check_launch(fn);

@@ -6,11 +6,15 @@ JSON line.
 
     python examples/run_tracking_ensemble.py [--data Data] [--members 65536] [--sigma 1e-3 1e-3 1e-2 1e-4 1e-3 1e-4]
                                              [--delta 0.3 0.3 0.5 0.05 0.1 0.05] [--seed 1] [--dt 1e-3]
-                                             [--envelope FILE.npz]
+                                             [--envelope FILE.npz] [--quantiles FILE.npz [--q 0.05 0.5 0.95]]
 
 --envelope FILE.npz: also reduce over the members at every sample on the device (the tube around the optimum) and save
 n (T,), min_dx / max_dx (6,T), min_du / max_du (2,T), mean_dx (6,T), cov_dx (6,6,T), raw (T,44); the JSON line then
 carries "envelope": the file, n at the last sample and the largest band width max_dx - min_dx per state.
+--quantiles FILE.npz: also the quantile tubes --q over the members at every sample, from a 64-bin histogram counted on the
+device in a second pass over the same members (bins from the min / max of the first), and save quantiles (len(q),), n (T,),
+hist (T,8,64), bins (T,8,2) = (lo, inv_w), tube (len(q),8,T), tube_width (8,T) (channels dx[0..5], du[0..1]); the JSON
+line then carries "quantiles": the file, q and the largest width of the tube (last level - first level) per state.
 """
 import argparse
 import json
@@ -32,6 +36,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dt", type=float, default=1e-3)
     ap.add_argument("--envelope", default=None, metavar="FILE.npz", help="save the per-sample envelope over the members")
+    ap.add_argument("--quantiles", default=None, metavar="FILE.npz", help="save per-sample quantile tubes over the members")
+    ap.add_argument("--q", type=float, nargs="+", default=[0.05, 0.5, 0.95], help="quantile levels of --quantiles")
     a = ap.parse_args()
     xx_opt = np.load(os.path.join(a.data, "xx_star.npy"))
     uu_opt = np.load(os.path.join(a.data, "uu_star.npy"))
@@ -39,7 +45,8 @@ def main():
     Q, R, QT = problems.tracking_weights()                           # lqr_tracking.py:324-328
     bp = batch.BatchProblem(Q, R, QT, np.zeros((6, T)), np.zeros((2, T)), a.dt)
     delta = np.random.default_rng(a.seed).normal(size=(a.members, 6)) * np.asarray(a.delta)
-    r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, envelope=a.envelope is not None)
+    r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, envelope=a.envelope is not None,
+                             quantiles=a.q if a.quantiles is not None else None)
     sm = r["summary"][0]
     tolist = lambda d: {k: np.asarray(v).tolist() for k, v in d.items()}
     line = dict(members=a.members, T=T, sigma=a.sigma, left_the_domain=sm["n_bad"],
@@ -51,6 +58,14 @@ def main():
         width = (env["max_dx"] - env["min_dx"])[:, some]
         line["envelope"] = dict(file=a.envelope, n_last=int(env["n"][-1]),
                                 max_width=width.max(axis=1).tolist() if some.any() else None)
+    if a.quantiles is not None:
+        tube = r["tube"][0]
+        np.savez(a.quantiles, quantiles=np.asarray(r["quantiles"]), n=r["envelope"][0]["n"], hist=r["hist"][0], bins=r["bins"][0],
+                 tube=tube, tube_width=r["tube_width"][0])
+        with np.errstate(all="ignore"):
+            span = tube[-1, :6] - tube[0, :6]                        # NaN where no member counts
+        line["quantiles"] = dict(file=a.quantiles, q=list(r["quantiles"]),
+                                 max_tube_width=np.nanmax(span, axis=1).tolist() if np.isfinite(span).any() else None)
     print(json.dumps(line))
 
 

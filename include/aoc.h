@@ -60,6 +60,8 @@ extern "C" {
  *      half it is solved in); aoc_tuning.fw_wpe1, hcut_chain6, bw_hcut_full, fw_duo, hcut_waves, hcut_pairs
  *      (still 5, an addition: aoc_track_ensemble — no struct, argument list or size query changed)
  *      (still 5, an addition: aoc_track_ensemble_envelope, aoc_ensemble_envelope_scratch_bytes — no struct, argument list
+ *      or size query of an existing entry changed)
+ *      (still 5, an addition: aoc_track_ensemble_histogram, aoc_ensemble_histogram_scratch_bytes — no struct, argument list
  *      or size query of an existing entry changed) */
 #define AOC_ABI_VERSION 5
 
@@ -558,6 +560,40 @@ int aoc_track_ensemble_envelope(const aoc_problem *prob, int32_t n_opt, int32_t 
                                 const double *x0_reg, const aoc_mpc_noise *noise, void *x_reg, double *u_reg,
                                 double *dist_out, double *stats, int32_t *status, double *envelope, void *scratch,
                                 size_t scratch_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The same ensemble once more, COUNTED over the members at every sample: a fixed-bin histogram per optimum, sample and
+ * channel, from which quantile tubes follow on the host.  An ensemble is a function of (seed, global member index, step)
+ * alone, so a second call sees the values of the first bit for bit: bins built from the min / max of an
+ * aoc_track_ensemble_envelope call cover exactly the values this call bins.  Every argument that aoc_track_ensemble has
+ * means what it means there and is checked as there, and every output the calls share (x_reg, u_reg, dist_out, stats,
+ * status) has the same bits from either.
+ * bins: DEVICE, fp64, [n_opt][T][AOC_HIST_NCH][2] = (lo, inv_w) per optimum, sample and channel, not NULL.  Channels:
+ *   0-5 dx[c] = x_t[c] - x_opt_t[c], 6-7 du[r] = u_t[r] - u_opt_t[r].
+ * hist: DEVICE, int32, [n_opt][T][AOC_HIST_NCH][AOC_HIST_NBIN], not NULL, 16-byte aligned, written in full.  A member b of
+ *   optimum k COUNTS
+ *   at sample t under the envelope's rule — b < B (the lanes of the last tile that replicate member B-1 never count) and
+ *   t < stats[15] of b — and then adds 1 to bin k of every channel, with v the channel's value:
+ *       s = (v - lo) * inv_w          two fp64 operations, each rounded (no fused multiply-add)
+ *       k = s >= 63 ? 63 : (s >= 1 ? (int)s : 0)
+ *   The end bins absorb everything outside [lo, lo + 64 / inv_w); a NaN s (bins that are not finite) lands in bin 0; no
+ *   conversion is ever undefined.  inv_w = 0 puts every member into bin 0.  Sample T-1 has no input: channels 6 and 7 are
+ *   all zero there.  A member that does not count adds nothing.
+ *   Counts are integers: the result is exact and does not depend on order, run, or whether trajectories are written, and
+ *   counts of disjoint member sets under the same bins (calls cut with noise->first, shards, devices) merge by addition.
+ * scratch: DEVICE, caller-owned, 16-byte aligned, at least aoc_ensemble_histogram_scratch_bytes(B, T, members_per_opt)
+ *   bytes (one byte per tile, sample, channel and bin: 512 * T * ceil(B / 64)); NULL, misaligned or too small is
+ *   AOC_EINVAL with the reason.  Nothing is allocated.
+ * Two kernels on prob->stream: the ensemble kernel, whose lanes count into byte counters in LDS that the wavefront drains
+ * to the tile's partial every few samples, then the fold over the tiles of each optimum.
+ * --------------------------------------------------------------------------------------------- */
+#define AOC_HIST_NCH  8    /* dx[0..5], du[0..1] */
+#define AOC_HIST_NBIN 64
+size_t aoc_ensemble_histogram_scratch_bytes(int32_t B, int32_t T, int32_t members_per_opt);
+int aoc_track_ensemble_histogram(const aoc_problem *prob, int32_t n_opt, int32_t members_per_opt, const double *nominal,
+                                 const double *x0_reg, const aoc_mpc_noise *noise, const double *bins, void *x_reg,
+                                 double *u_reg, double *dist_out, double *stats, int32_t *status, int32_t *hist,
+                                 void *scratch, size_t scratch_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * float32 arithmetic (BASELINE.json configs[2]: "fp32 with tolerance sweep").

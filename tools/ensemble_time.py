@@ -2,6 +2,7 @@
 """Closed-loop tracking ensemble about ONE optimum: aoc_track_ensemble against the replicated path it replaces.
 
     python tools/ensemble_time.py [--members 65536 262144] [--T 1000] [--seconds 0.5] [--repeats 3] [--out FILE]
+                                  [--envelope] [--histogram]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/ensemble_time.py --trace --members N
     python tools/ensemble_time.py --kernel-times DIR                 (kernel times: a traced run of its own, then its summary)
 
@@ -16,6 +17,17 @@
              tiles — the fastest of four forms tried, EXPERIMENTS.md)
   B_env      aoc_track_ensemble_envelope, statistics + envelope, no trajectories
 and reports E = E_traj + E_reduce, B_env / E and B_env / B_stats (the price of the reduction).
+--histogram adds the per-sample histogram over the members (aoc_track_ensemble_histogram, 8 x 64 counts per sample):
+  H          aoc_track_ensemble_histogram, statistics + counts, no trajectories, under the bins of the envelope's min / max
+  H_one_bin  the same call under bins with inv_w = 0: all 64 lanes of a tile add to ONE dword of LDS at every sample and
+             channel, the worst case of the serialised adds
+  Q_traj     the only way without it, part 1: aoc_track_ensemble writing x_reg and u_reg in fp64 (no dist_out)
+  Q_count    ... part 2, the same counts with torch on the tiled device arrays: the bin of every value, then one
+             scatter_add_ of ones per 256 tiles
+  Q_sort     ... part 2 the other way, the three quantiles 0.05 / 0.5 / 0.95 themselves: torch.quantile over the members
+             of dx and du (a sort per sample and channel), no mask for members that left
+and reports C = B_stats, E = B_env, Q = Q_traj + min(Q_count, Q_sort), H/C, H/E and H/Q; --hist-valu, the vector
+instructions of one stage of the H kernel from the ISA, gives its share of the vector-issue roof as --valu does for B_stats.
 The optimum is the g4 fixture's (T = 1000; --T cuts it), the members are seeded perturbations of its first sample.
 Profiler off: HIP events around at least --seconds of back-to-back launches per variant, after a warm-up of every variant;
 the variants take turns inside each of --repeats rounds, so that a drift of the machine hits all of them.  One JSON line:
@@ -40,7 +52,7 @@ DELTA_SCALE = np.array([0.3, 0.3, 0.5, 0.05, 0.1, 0.05])
 SIGMA = np.array([1e-3, 1e-3, 1e-2, 1e-4, 1e-3, 1e-4])
 
 
-def setup(B, T, g, envelope=False):
+def setup(B, T, g, envelope=False, histogram=False):
     """Device buffers and the launch closures for B members."""
     import torch
     from aircraftoptimalcontrol_amd import _lib, batch
@@ -78,7 +90,7 @@ def setup(B, T, g, envelope=False):
                                        _ptr(status)), "aoc_track_ensemble")
 
     runs = dict(A=run_A, B_stats=run_B, B_traj=lambda: run_B(traj=True), B_noise=lambda: run_B(noise=True))
-    if not envelope:
+    if not envelope and not histogram:
         return runs
     # E: trajectories in fp64 + a torch reduction on the tiled arrays [tile][t][c][lane]
     xr64, ur64 = alloc_tiled(B, T, 6, dev), alloc_tiled(B, T, 2, dev)
@@ -129,7 +141,68 @@ def setup(B, T, g, envelope=False):
     got = env[0]
     assert torch.equal(got[:, :17], want[:, :17]), "E and B_env disagree in n / min / max"
     assert bool(((got[:, 17:] - want[:, 17:]).abs() <= 1e-9 * want[:, 17:].abs().max()).all()), "E and B_env disagree in the sums"
-    runs.update(E_traj=run_E_traj, E_reduce=run_E_reduce, B_env=run_B_env)
+    if envelope:
+        runs.update(E_traj=run_E_traj, E_reduce=run_E_reduce)
+    runs.update(B_env=run_B_env)
+    if not histogram:
+        return runs
+    # H: the second pass under the bins of the first; Q: trajectories in fp64 + torch, to the same counts or to quantiles
+    NCH, NBIN = _lib.AOC_HIST_NCH, _lib.AOC_HIST_NBIN
+    bins = torch.from_numpy(batch.histogram_bins(env.cpu().numpy())).to(dev)                  # (1,T,8,2)
+    hist = torch.empty((1, T, NCH, NBIN), dtype=torch.int32, device=dev)
+    hbytes = int(lib().aoc_ensemble_histogram_scratch_bytes(B, T, nt * TILE))
+    hscratch = torch.empty(max(hbytes, 8) // 8, dtype=torch.float64, device=dev)
+
+    def run_H():
+        check(lib().aoc_track_ensemble_histogram(C.byref(pB), 1, nt * TILE, _ptr(nominal), _ptr(x0t), None, _ptr(bins), None, None,
+                                                 None, _ptr(stats), _ptr(status), _ptr(hist), _ptr(hscratch), hbytes),
+              "aoc_track_ensemble_histogram")
+
+    bins_one = bins.clone()
+    bins_one[..., 1] = 0.0
+    hist_one = torch.empty_like(hist)
+
+    def run_H_one_bin():
+        check(lib().aoc_track_ensemble_histogram(C.byref(pB), 1, nt * TILE, _ptr(nominal), _ptr(x0t), None, _ptr(bins_one), None,
+                                                 None, None, _ptr(stats), _ptr(status), _ptr(hist_one), _ptr(hscratch), hbytes),
+              "aoc_track_ensemble_histogram")
+
+    lo, inv_w = bins[0, :, :, 0].contiguous(), bins[0, :, :, 1].contiguous()                  # (T,8)
+    slot = (torch.arange(T, device=dev, dtype=torch.int32).view(1, T, 1, 1) * NCH
+            + torch.arange(NCH, device=dev, dtype=torch.int32).view(1, 1, NCH, 1)) * NBIN     # (1,T,8,1)
+    dump = T * NCH * NBIN                                                                     # where what does not count goes
+    CH = 256
+
+    def run_Q_count():
+        xv, uv = xr64.view(nt, T, 6, TILE), ur64.view(nt, T, 2, TILE)
+        acc = torch.zeros(dump + 1, dtype=torch.int32, device=dev)
+        for i in range(0, nt, CH):
+            v = torch.cat([xv[i:i + CH] - xo_d.view(1, T, 6, 1), uv[i:i + CH] - uo_d.view(1, T, 2, 1)], dim=2)   # (ch,T,8,64)
+            s = (v - lo.view(1, T, NCH, 1)) * inv_w.view(1, T, NCH, 1)
+            k = torch.where(s >= 63.0, 63.0, torch.where(s >= 1.0, s, 0.0)).to(torch.int32)
+            counts = ((tt.view(1, T, 1) < stats[i:i + CH, 15, :].view(-1, 1, TILE)) & live[i:i + CH]).unsqueeze(2)
+            idx = torch.where(counts, slot + k, dump)
+            idx[:, T - 1, 6:, :] = dump
+            acc.scatter_add_(0, idx.view(-1).to(torch.int64), torch.ones((), dtype=torch.int32, device=dev).expand(idx.numel()))
+        return acc[:dump].view(T, NCH, NBIN)
+
+    qq = torch.tensor([0.05, 0.5, 0.95], dtype=torch.float64, device=dev)
+
+    def run_Q_sort():
+        xv, uv = xr64.view(nt, T, 6, TILE), ur64.view(nt, T, 2, TILE)
+        out = torch.empty((3, T, NCH), dtype=torch.float64, device=dev)
+        for c in range(NCH):          # channel by channel: one (T, members) array at a time
+            v = (xv[:, :, c, :] - xo_d[:, c].view(1, T, 1)) if c < 6 else (uv[:, :, c - 6, :] - uo_d[:, c - 6].view(1, T, 1))
+            v = v.permute(1, 0, 2).reshape(T, nt * TILE)
+            out[:, :, c] = torch.sort(v, dim=1).values[:, ((qq * (nt * TILE)).ceil().clamp(min=1) - 1).long()].T
+        return out
+
+    # the two ways to the counts agree before either is timed
+    run_E_traj(); want = run_Q_count(); run_H(); torch.cuda.synchronize()
+    assert torch.equal(hist[0], want), "Q_count and H disagree"
+    run_H_one_bin(); torch.cuda.synchronize()
+    assert int(hist_one[..., 0].sum()) == int(hist_one.sum()) == int(hist.sum()), "H_one_bin: not everything in bin 0"
+    runs.update(H=run_H, H_one_bin=run_H_one_bin, Q_traj=run_E_traj, Q_count=run_Q_count, Q_sort=run_Q_sort)
     return runs
 
 
@@ -179,6 +252,8 @@ def main():
     ap.add_argument("--trace", action="store_true", help="three calls per variant and nothing else (under rocprofv3)")
     ap.add_argument("--kernel-times", default=None, metavar="DIR", help="summarise the kernel trace(s) under DIR (no GPU)")
     ap.add_argument("--envelope", action="store_true", help="also time the per-sample envelope: E_traj + E_reduce against B_env")
+    ap.add_argument("--histogram", action="store_true", help="also time the per-sample histogram: H against B_stats, B_env and Q")
+    ap.add_argument("--hist-valu", type=int, default=0, help="vector instructions per stage of the histogram kernel (from the ISA)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.kernel_times:
@@ -191,7 +266,7 @@ def main():
     for B in a.members:
         rec = dict(members=B)
         try:
-            runs = setup(B, a.T, g, a.envelope)
+            runs = setup(B, a.T, g, a.envelope, a.histogram)
         except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
             rec["refused"] = "allocation refused: %s" % str(e).split("\n")[0]
             out["sizes"].append(rec)
@@ -218,6 +293,17 @@ def main():
                 E = med["E_traj"] + med["E_reduce"]
                 rec["envelope"] = dict(E_ms=round(E, 4), B_env_over_E=round(med["B_env"] / E, 4),
                                        B_env_over_B_stats=round(med["B_env"] / med["B_stats"], 4))
+            if a.histogram:
+                Q = med["Q_traj"] + min(med["Q_count"], med["Q_sort"])
+                spread = lambda k: round((max(ms[k]) - min(ms[k])) / med[k], 4)
+                rec["histogram"] = dict(H_ms=med["H"], C_ms=med["B_stats"], E_ms=med["B_env"], Q_ms=round(Q, 4),
+                                        H_over_C=round(med["H"] / med["B_stats"], 4), H_over_E=round(med["H"] / med["B_env"], 4),
+                                        H_over_Q=round(med["H"] / Q, 4), H_one_bin_over_H=round(med["H_one_bin"] / med["H"], 4),
+                                        spread_rel=dict(H=spread("H"), C=spread("B_stats"), E=spread("B_env")))
+                if a.hist_valu:
+                    roof = (B / 64) * (a.T - 1) * a.hist_valu * CYCLES_PER_VALU / (SIMDS * CLOCK_HZ) * 1e3
+                    rec["histogram"]["vector_issue"] = dict(valu_per_stage=a.hist_valu, roof_ms=round(roof, 4),
+                                                            share_H=round(roof / med["H"], 3))
             stages = B * (a.T - 1)
             rec["member_stages_per_s"] = {k: round(stages / (med[k] * 1e-3), 0) for k in ms}
             if a.valu:
