@@ -985,6 +985,7 @@ ENS_QUANTILES = (0.5, 0.9, 0.99)
 ENV_NREC = _lib.AOC_ENV_NREC       # doubles per (optimum, sample) record of aoc_track_ensemble_envelope
 HIST_NCH = _lib.AOC_HIST_NCH       # channels of aoc_track_ensemble_histogram: dx[0..5], du[0..1]
 HIST_NBIN = _lib.AOC_HIST_NBIN     # bins per (optimum, sample, channel)
+COV_NREC = _lib.AOC_COV_NREC       # doubles per (optimum, sample) record of aoc_track_covariance
 # the record (include/aoc.h): n | min dx | max dx | min du | max du | sum dx | sum dx_i dx_j (upper triangle, row by row)
 _ENV_MIN = np.r_[1:7, 13:15]
 _ENV_MAX = np.r_[7:13, 15:17]
@@ -1135,6 +1136,117 @@ def histogram_quantiles(hist, bins, q):
     return np.ascontiguousarray(tube.transpose(0, 1, 3, 2)), np.ascontiguousarray(width.transpose(0, 2, 1))
 
 
+def covariance_moments(raw):
+    """Records (T, 32) of aoc_track_covariance -> mean_dx (6,T), cov_dx (6,6,T), mean_du (2,T), cov_du (2,2,T): what linear
+    theory predicts for dx = x - x_opt and du = u - u_opt (sample T-1 of the input moments is 0: there is no input).
+    NumPy only, needs no GPU."""
+    raw = np.asarray(raw, dtype=np.float64)
+    if raw.ndim != 2 or raw.shape[1] != COV_NREC:
+        raise ValueError("records (T, %d) expected, got %s" % (COV_NREC, raw.shape))
+    T = raw.shape[0]
+    cov = np.empty((T, 6, 6))
+    cov[:, _ENV_TRI[0], _ENV_TRI[1]] = raw[:, 6:27]
+    cov[:, _ENV_TRI[1], _ENV_TRI[0]] = raw[:, 6:27]
+    cu = np.empty((T, 2, 2))
+    cu[:, 0, 0], cu[:, 0, 1], cu[:, 1, 0], cu[:, 1, 1] = raw[:, 29], raw[:, 30], raw[:, 30], raw[:, 31]
+    return (np.ascontiguousarray(raw[:, 0:6].T), np.ascontiguousarray(cov.transpose(1, 2, 0)),
+            np.ascontiguousarray(raw[:, 27:29].T), np.ascontiguousarray(cu.transpose(1, 2, 0)))
+
+
+def _covariance_dict(raw):
+    mean_dx, cov_dx, mean_du, cov_du = covariance_moments(raw)
+    return dict(mean_dx=mean_dx, cov_dx=cov_dx, mean_du=mean_du, cov_du=cov_du, raw=raw)
+
+
+_COV_MEAN = np.r_[0:6, 27:29]                                                       # the eight channels' means ...
+_COV_VAR = np.r_[[6 + int(i * 6 - i * (i - 1) // 2) for i in range(6)], 29, 31]     # ... and variances in a record
+
+
+def histogram_bins_predicted(raw, k=6.0):
+    """Bins from the prediction instead of a first pass: records (n_opt,T,32) (or (T,32)) of aoc_track_covariance -> bins
+    (n_opt,T,8,2) = (lo, inv_w) per optimum, sample and channel (dx[0..5], du[0..1]): lo = mean - k std, inv_w =
+    64 / (2 k std).  Where std is 0 or not finite (a channel nothing moves; du at sample T-1) the bins are (mean, 0), and
+    (0, 0) if the mean is not finite either: everything then goes to bin 0.  NumPy only, needs no GPU."""
+    raw = np.asarray(raw, dtype=np.float64)
+    raw = raw[None] if raw.ndim == 2 else raw
+    if raw.ndim != 3 or raw.shape[2] != COV_NREC:
+        raise ValueError("records (n_opt, T, %d) expected, got %s" % (COV_NREC, raw.shape))
+    k = float(k)
+    if not k > 0:
+        raise ValueError("k = %r (need k > 0)" % (k,))
+    mean, var = raw[..., _COV_MEAN], raw[..., _COV_VAR]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        std = np.sqrt(var)
+        w = 2.0 * k * std
+        ok = np.isfinite(mean) & np.isfinite(w) & (w > 0)
+        inv_w = np.where(ok, HIST_NBIN / w, 0.0)
+        ok &= np.isfinite(inv_w)
+        lo = np.where(ok, mean - k * std, np.where(np.isfinite(mean), mean, 0.0))
+    return np.ascontiguousarray(np.stack([lo, np.where(ok, inv_w, 0.0)], axis=-1))
+
+
+def _sym_upper(Sigma0, n_opt):
+    """(6,6) or (n_opt,6,6), symmetric (checked) -> (n_opt,21) upper triangle row by row"""
+    S = np.asarray(Sigma0, dtype=np.float64)
+    S = np.broadcast_to(S, (n_opt, 6, 6)) if S.ndim == 2 else S
+    if S.shape != (n_opt, 6, 6):
+        raise ValueError("Sigma0 must be (6,6) or (n_opt,6,6) with n_opt = %d, got %s" % (n_opt, S.shape))
+    if not np.array_equal(S, S.transpose(0, 2, 1)):
+        raise ValueError("Sigma0 is not symmetric")
+    return np.ascontiguousarray(S[:, _ENV_TRI[0], _ENV_TRI[1]])
+
+
+def _predict_covariance(problem, nominal, n_opt, mean0, Sigma0, sigma):
+    """aoc_track_covariance on a device `nominal` (n_opt,T,20) -> records (n_opt,T,32) numpy, status (n_opt,)"""
+    torch = _torch()
+    dev, T = problem.device, problem.T
+    m0 = S0 = None
+    if mean0 is not None:
+        m = np.asarray(mean0, dtype=np.float64)
+        m = np.broadcast_to(m, (n_opt, 6)) if m.ndim == 1 else m
+        if m.shape != (n_opt, 6):
+            raise ValueError("mean0 must be (6,) or (n_opt,6) with n_opt = %d, got %s" % (n_opt, m.shape))
+        m0 = _dev_f64(m, dev)
+    if Sigma0 is not None:
+        S0 = _dev_f64(_sym_upper(Sigma0, n_opt), dev)
+    nz = None
+    if sigma is not None:
+        nz = _lib.MpcNoise(0, 0, 0, (C.c_double * 6)(*np.asarray(sigma, dtype=np.float64).tolist()))
+    pred = torch.empty((n_opt, T, COV_NREC), dtype=torch.float64, device=dev)
+    status = torch.zeros(n_opt, dtype=torch.int32, device=dev)
+    nbytes = int(lib().aoc_track_covariance_scratch_bytes(n_opt, T))
+    scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    p = problem.c_problem(n_opt)
+    check(lib().aoc_track_covariance(C.byref(p), n_opt, _ptr(nominal), _ptr(m0), _ptr(S0), C.byref(nz) if nz is not None else None,
+                                     _ptr(pred), _ptr(status), _ptr(scratch), nbytes), "aoc_track_covariance")
+    return pred.cpu().numpy(), status.cpu().numpy()
+
+
+def predict_covariance(problem, xx_opt, uu_opt, KK=None, mean0=None, Sigma0=None, sigma=None):
+    """What linear theory predicts for a closed-loop tracking ensemble about each optimum (aoc_track_covariance): the mean
+    and covariance of dx = x - x_opt and of du = u - u_opt at every sample, from the Lyapunov recursion with the tracking
+    gains, m' = F m + c, P' = F P F^T + diag(sigma^2), F = A + B K (include/aoc.h).  xx_opt (6,T) or (n_opt,6,T), uu_opt
+    likewise; KK=None: gains from tracking_gains; mean0 (6,) or (n_opt,6) and Sigma0 (6,6) or (n_opt,6,6) (symmetric,
+    checked here) are the moments of dx at sample 0, None = 0; sigma (6,) the std of the disturbance, None = none.
+    Returns (list per optimum of dict(mean_dx (6,T), cov_dx (6,6,T), mean_du (2,T), cov_du (2,2,T), raw (T,32)),
+    status (n_opt,))."""
+    torch = _torch()
+    xo, uo = np.asarray(xx_opt, dtype=np.float64), np.asarray(uu_opt, dtype=np.float64)
+    if xo.ndim == 2:
+        xo, uo = xo[None], uo[None]
+    n_opt, T = xo.shape[0], problem.T
+    if xo.shape != (n_opt, 6, T) or uo.shape != (n_opt, 2, T):
+        raise ValueError("xx_opt must be (6,T) or (n_opt,6,T) with T = %d, uu_opt likewise" % T)
+    if KK is None:
+        KK, _ = tracking_gains(problem, xo, uo)
+    else:
+        KK = np.asarray(KK, dtype=np.float64)
+        KK = KK[None] if KK.ndim == 3 else KK
+    nominal = torch.from_numpy(ensemble_nominal(xo, uo, KK)).to(problem.device)
+    raw, status = _predict_covariance(problem, nominal, n_opt, mean0, Sigma0, sigma)
+    return [_covariance_dict(r) for r in raw], status
+
+
 def _ens_summary(torch, v):
     """mean / max / quantiles over the members (rows) of one optimum, reduced on the device"""
     q = torch.quantile(v, torch.tensor(ENS_QUANTILES, dtype=v.dtype, device=v.device), dim=0)
@@ -1145,7 +1257,7 @@ def _ens_summary(torch, v):
 
 def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, sigma=None, seed=20260405, first=0,
                    step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True, envelope=False,
-                   quantiles=None, bins=None):
+                   quantiles=None, bins=None, predict=False, mean0=None, Sigma0=None, predict_k=6.0):
     """Closed-loop tracking ensemble about shared optima (aoc_track_ensemble): the loop of lqr_tracking.py:279-281 for B
     members, u_t = u_opt_t + K_t (x_t - x_opt_t), x_{t+1} = step(x_t, u_t) + d_t, reduced to per-member statistics on
     the device; the optimum and its gains are stored once per optimum, not once per member.
@@ -1171,7 +1283,15 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     (n_opt,T,8,2) (or (T,8,2)) = (lo, inv_w): the caller's own — fixed corridors, or the common bins of a sharded job,
     whose counts histogram_merge adds — and no envelope call (unless envelope=True asks for it).  Adds, each a list per
     optimum: hist (T,8,64) int32, bins (T,8,2), tube (len(quantiles),8,T) and tube_width (8,T) (histogram_quantiles:
-    bin midpoints and the bin width, the resolution), and `quantiles` as given."""
+    bin midpoints and the bin width, the resolution), and `quantiles` as given.
+    predict=True (aoc_track_covariance; every other output keeps its bits): also `predicted`, per optimum what linear theory
+    gives for the same loop, dict(mean_dx (6,T), cov_dx (6,6,T), mean_du (2,T), cov_du (2,2,T), raw (T,32)) as
+    predict_covariance, and `predicted_status` (n_opt,).  mean0 (6,) / (n_opt,6) and Sigma0 (6,6) / (n_opt,6,6): the
+    moments of dx at sample 0; None: the population mean and covariance of each group's own initial deviations, computed
+    on the host.  The disturbance is the call's own sigma.
+    bins="predicted" (with quantiles=): the bins are histogram_bins_predicted of that prediction, mean -+ predict_k std, so
+    the histogram call is the ONLY pass over the members — no envelope call unless envelope=True asks for it — and
+    `predicted` is returned as well."""
     torch = _torch()
     dev = problem.device
     xo, uo = np.asarray(xx_opt, dtype=np.float64), np.asarray(uu_opt, dtype=np.float64)
@@ -1208,6 +1328,21 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     p = problem.c_problem(B, x_out_f32=int(bool(f32)))
     nzp = C.byref(nz) if nz is not None else None
     hist = quantiles is not None
+    bins_predicted = isinstance(bins, str)
+    if bins_predicted:
+        if bins != "predicted" or not hist:
+            raise ValueError('bins=%r: the only name is "predicted", and it goes with quantiles=' % (bins,))
+        predict = True
+    if predict:
+        dx0 = x0 - xo[group, :, 0]
+        if mean0 is None:
+            mean0 = np.stack([dx0[group == k].mean(axis=0) for k in range(n_opt)])
+        if Sigma0 is None:
+            Sigma0 = np.stack([np.cov(dx0[group == k].T, bias=True).reshape(6, 6) for k in range(n_opt)])
+            Sigma0 = 0.5 * (Sigma0 + Sigma0.transpose(0, 2, 1))
+        pred_raw, pred_status = _predict_covariance(problem, nominal, n_opt, mean0, Sigma0, sigma)
+        if bins_predicted:
+            bins = histogram_bins_predicted(pred_raw, predict_k)
     if hist:
         quantiles = tuple(float(f) for f in np.atleast_1d(np.asarray(quantiles, dtype=np.float64)))
         if bins is not None:
@@ -1262,6 +1397,8 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
                status=status[:B].cpu().numpy(), stats=s, members_per_opt=mpo, group=group, summary=summary)
     if envelope:
         out["envelope"] = [_envelope_dict(r) for r in env.cpu().numpy()]
+    if predict:
+        out.update(predicted=[_covariance_dict(r) for r in pred_raw], predicted_status=pred_status)
     if hist:
         counts = hist_d.cpu().numpy()
         tube, width = histogram_quantiles(counts, bins, quantiles)

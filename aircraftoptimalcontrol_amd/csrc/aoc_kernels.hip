@@ -7,7 +7,7 @@
 // No MFMA (the blocks are 6x6/6x2); the per-lane state (P: 21, p: 6, lambda: 6 doubles, ...) lives in VGPRs.
 // The kernels themselves are in aoc_passes.inc (which includes passes/*.inc, one file per pass: layout, unit, cost_rollout,
 // backward, forward, tracking, hcut, ltv_lqr, linesearch, mpc; then the launch functions api.inc and the solve loop
-// solve.inc, and ensemble.inc with its own launch function) + aoc_device.h, compiled twice: fp64 (aoc64, the parity path) and float32 (aoc32, BASELINE config 3); this file
+// solve.inc, and ensemble.inc and covariance.inc with their own launch functions) + aoc_device.h, compiled twice: fp64 (aoc64, the parity path) and float32 (aoc32, BASELINE config 3); this file
 // holds what is common and the C-ABI.
 #include <hip/hip_runtime.h>
 
@@ -540,6 +540,17 @@ int aoc_track_ensemble_histogram(const aoc_problem* p, int32_t n_opt, int32_t me
     static_assert(aoc64::HIST_NCH == AOC_HIST_NCH && aoc64::HIST_NBIN == AOC_HIST_NBIN, "histogram of the kernel and of the header");
     return aoc64::api_track_ensemble("aoc_track_ensemble_histogram", aoc64::ENS_HISTOGRAM, p, n_opt, members_per_opt, nominal, x0_reg,
                                      noise, x_reg, u_reg, dist_out, stats, status, nullptr, bins, hist, scratch, scratch_bytes);
+}
+
+size_t aoc_track_covariance_scratch_bytes(int32_t n_opt, int32_t T) {
+    return aoc64::track_covariance_scratch_bytes(n_opt, T);
+}
+
+int aoc_track_covariance(const aoc_problem* p, int32_t n_opt, const double* nominal, const double* mean0,
+                         const double* Sigma0, const aoc_mpc_noise* noise, double* pred, int32_t* status, void* scratch,
+                         size_t scratch_bytes) {
+    static_assert(aoc64::COV_NREC == AOC_COV_NREC, "prediction record of the kernel and of the header");
+    return aoc64::api_track_covariance(p, n_opt, nominal, mean0, Sigma0, noise, pred, status, scratch, scratch_bytes);
 }
 
 // ---- float32 arithmetic (aoc32): every array, the reference curves and the workspace are float32 ------

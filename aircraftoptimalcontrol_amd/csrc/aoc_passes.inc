@@ -21,5 +21,6 @@ namespace AOC_ARITH_NS {
 #include "passes/solve.inc"
 #endif  // AOC_KERNELS_ONLY
 #include "passes/ensemble.inc"   // kernel and launch function in one file (the latter uses make_const of api.inc)
+#include "passes/covariance.inc" // likewise (the nominal's record is that of ensemble.inc)
 
 }  // namespace AOC_ARITH_NS

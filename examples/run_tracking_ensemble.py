@@ -7,6 +7,7 @@ JSON line.
     python examples/run_tracking_ensemble.py [--data Data] [--members 65536] [--sigma 1e-3 1e-3 1e-2 1e-4 1e-3 1e-4]
                                              [--delta 0.3 0.3 0.5 0.05 0.1 0.05] [--seed 1] [--dt 1e-3]
                                              [--envelope FILE.npz] [--quantiles FILE.npz [--q 0.05 0.5 0.95]]
+                                             [--predict FILE.npz]
 
 --envelope FILE.npz: also reduce over the members at every sample on the device (the tube around the optimum) and save
 n (T,), min_dx / max_dx (6,T), min_du / max_du (2,T), mean_dx (6,T), cov_dx (6,6,T), raw (T,44); the JSON line then
@@ -15,6 +16,10 @@ carries "envelope": the file, n at the last sample and the largest band width ma
 device in a second pass over the same members (bins from the min / max of the first), and save quantiles (len(q),), n (T,),
 hist (T,8,64), bins (T,8,2) = (lo, inv_w), tube (len(q),8,T), tube_width (8,T) (channels dx[0..5], du[0..1]); the JSON
 line then carries "quantiles": the file, q and the largest width of the tube (last level - first level) per state.
+--predict FILE.npz: also what linear theory predicts for the same loop (the Lyapunov recursion about the optimum with the
+tracking gains, from the population moments of the initial perturbation, --delta, and --sigma) and save mean_dx (6,T),
+cov_dx (6,6,T), mean_du (2,T), cov_du (2,2,T), raw (T,32): the tube the sampled one of --envelope is read against; the JSON
+line then carries "predict": the file and the largest predicted standard deviation per state.
 """
 import argparse
 import json
@@ -37,6 +42,7 @@ def main():
     ap.add_argument("--dt", type=float, default=1e-3)
     ap.add_argument("--envelope", default=None, metavar="FILE.npz", help="save the per-sample envelope over the members")
     ap.add_argument("--quantiles", default=None, metavar="FILE.npz", help="save per-sample quantile tubes over the members")
+    ap.add_argument("--predict", default=None, metavar="FILE.npz", help="save the linear prediction of mean and covariance")
     ap.add_argument("--q", type=float, nargs="+", default=[0.05, 0.5, 0.95], help="quantile levels of --quantiles")
     a = ap.parse_args()
     xx_opt = np.load(os.path.join(a.data, "xx_star.npy"))
@@ -46,7 +52,8 @@ def main():
     bp = batch.BatchProblem(Q, R, QT, np.zeros((6, T)), np.zeros((2, T)), a.dt)
     delta = np.random.default_rng(a.seed).normal(size=(a.members, 6)) * np.asarray(a.delta)
     r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, envelope=a.envelope is not None,
-                             quantiles=a.q if a.quantiles is not None else None)
+                             quantiles=a.q if a.quantiles is not None else None, predict=a.predict is not None,
+                             mean0=np.zeros(6), Sigma0=np.diag(np.asarray(a.delta) ** 2))
     sm = r["summary"][0]
     tolist = lambda d: {k: np.asarray(v).tolist() for k, v in d.items()}
     line = dict(members=a.members, T=T, sigma=a.sigma, left_the_domain=sm["n_bad"],
@@ -66,6 +73,11 @@ def main():
             span = tube[-1, :6] - tube[0, :6]                        # NaN where no member counts
         line["quantiles"] = dict(file=a.quantiles, q=list(r["quantiles"]),
                                  max_tube_width=np.nanmax(span, axis=1).tolist() if np.isfinite(span).any() else None)
+    if a.predict is not None:
+        pred = r["predicted"][0]
+        np.savez(a.predict, **pred)
+        std = np.sqrt(np.einsum("iit->it", pred["cov_dx"]))
+        line["predict"] = dict(file=a.predict, max_std=std.max(axis=1).tolist())
     print(json.dumps(line))
 
 

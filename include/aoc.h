@@ -62,7 +62,9 @@ extern "C" {
  *      (still 5, an addition: aoc_track_ensemble_envelope, aoc_ensemble_envelope_scratch_bytes — no struct, argument list
  *      or size query of an existing entry changed)
  *      (still 5, an addition: aoc_track_ensemble_histogram, aoc_ensemble_histogram_scratch_bytes — no struct, argument list
- *      or size query of an existing entry changed) */
+ *      or size query of an existing entry changed)
+ *      (still 5, an addition: aoc_track_covariance, aoc_track_covariance_scratch_bytes — no struct, argument list or size
+ *      query of an existing entry changed) */
 #define AOC_ABI_VERSION 5
 
 #define AOC_TILE 64
@@ -594,6 +596,42 @@ int aoc_track_ensemble_histogram(const aoc_problem *prob, int32_t n_opt, int32_t
                                  const double *x0_reg, const aoc_mpc_noise *noise, const double *bins, void *x_reg,
                                  double *u_reg, double *dist_out, double *stats, int32_t *status, int32_t *hist,
                                  void *scratch, size_t scratch_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * What LINEAR theory predicts for the same closed loop: the mean and covariance of dx = x - x_opt under the Lyapunov recursion
+ * about the optimum with the tracking gains — the number an ensemble's sampled moments are read against.  For t = 0 .. T-2,
+ *     A_t, B_t = the Jacobians of Dynamics.step at (x_opt_t, u_opt_t) (aoc_step_batch: fx = A^T, fu = B^T),
+ *     F_t = A_t + B_t K_t,      c_t = step(x_opt_t, u_opt_t) - x_opt_{t+1}   (the step in the plant's own arithmetic, float32
+ *                                     rounding included: exactly 0 for an optimum that is a rollout, the defect of one that is not)
+ *     m_{t+1} = F_t m_t + c_t,  P_{t+1} = F_t P_t F_t^T + W,   m_0 = mean0,  P_0 = Sigma0,  W = diag(sigma^2).
+ * Not modelled: the plant rounds every state to float32, which acts as further noise of about ulp(x) / sqrt(12) per step;
+ * the prediction is meaningful where sigma and the initial spread dominate that.
+ * prob: model (with dt), T and stream are read; B, the weights, ref and the x_* flags are not.
+ * nominal: DEVICE, [n_opt][T][20], the array aoc_track_ensemble takes.
+ * mean0: DEVICE, [n_opt][6], or NULL = 0.  Sigma0: DEVICE, [n_opt][21], the upper triangle row by row (the order of the
+ *   envelope's entries 23-43), or NULL = 0.
+ * noise: HOST, may be NULL (W = 0); only sigma[6] is read — the struct the ensemble calls take.
+ * pred: DEVICE, fp64, [n_opt][T][AOC_COV_NREC].  Record of optimum k at sample t:
+ *     0-5    m_t                                   6-26   upper triangle of P_t, row by row
+ *     27-28  K_t m_t, the mean of du               29-31  K_t P_t K_t^T, entries 00, 01, 11
+ *   Sample T-1 has no input: entries 27-31 are +0.0 there.  P is symmetric by construction (both halves are one expression).
+ *   With Sigma0 = NULL and noise = NULL the entries 6-26 and 29-31 are exactly +0.0 at every sample.
+ * status: DEVICE, [n_opt], may be NULL; OR-ed: AOC_ST_VNONPOS if !(V_opt_t > 0) at some t <= T-2, AOC_ST_NAN if an entry of
+ *   the optimum's records is not finite.  Such an optimum yields whatever the arithmetic gives and disturbs no other.
+ * scratch: DEVICE, caller-owned, 16-byte aligned, at least aoc_track_covariance_scratch_bytes(n_opt, T) bytes (0 for a
+ *   geometry the call refuses); the layout is private.  Nothing is allocated.
+ * AOC_EINVAL with the reason, before anything touches a device: prob, nominal or pred NULL; n_opt < 1; T < 3; scratch NULL,
+ * misaligned or too small.
+ * Two kernels on prob->stream: one lane per (optimum, sample) for everything that does not depend on the previous stage
+ * (sin / cos, Jacobians, the plant step, F_t, c_t), then one wavefront per optimum for the recursion, whose lanes own the
+ * entries of P and m.  No atomics, a fixed order: the same bits every run, and an optimum's record does not depend on n_opt or
+ * on its position in the call.
+ * --------------------------------------------------------------------------------------------- */
+#define AOC_COV_NREC 32
+size_t aoc_track_covariance_scratch_bytes(int32_t n_opt, int32_t T);
+int aoc_track_covariance(const aoc_problem *prob, int32_t n_opt, const double *nominal, const double *mean0,
+                         const double *Sigma0, const aoc_mpc_noise *noise, double *pred, int32_t *status, void *scratch,
+                         size_t scratch_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * float32 arithmetic (BASELINE.json configs[2]: "fp32 with tolerance sweep").

@@ -28,6 +28,13 @@ and reports E = E_traj + E_reduce, B_env / E and B_env / B_stats (the price of t
              of dx and du (a sort per sample and channel), no mask for members that left
 and reports C = B_stats, E = B_env, Q = Q_traj + min(Q_count, Q_sort), H/C, H/E and H/Q; --hist-valu, the vector
 instructions of one stage of the H kernel from the ISA, gives its share of the vector-issue roof as --valu does for B_stats.
+--predict adds the linear covariance prediction (aoc_track_covariance, 32 numbers per sample and optimum), for n_opt = 1, 64
+and 1024 windows of the optimum (--T at most 800 leaves room for them; otherwise the optimum is repeated):
+  P_n        aoc_track_covariance for n optima (both kernels)
+  TQ_n       the best torch route to the same 32 numbers: Jacobians from aoc_step_batch for all (optimum, stage) pairs, then
+             a stage loop of batched fp64 matmuls on the device (F P F^T + W, F m + c, K m, K P K^T)
+against B_stats and B_env of the same run (the cheapest Monte-Carlo answers), and the quantile route on the device: two
+passes B_env + H against one pass P_1 + H.
 The optimum is the g4 fixture's (T = 1000; --T cuts it), the members are seeded perturbations of its first sample.
 Profiler off: HIP events around at least --seconds of back-to-back launches per variant, after a warm-up of every variant;
 the variants take turns inside each of --repeats rounds, so that a drift of the machine hits all of them.  One JSON line:
@@ -206,6 +213,76 @@ def setup(B, T, g, envelope=False, histogram=False):
     return runs
 
 
+def setup_predict(T, g, sizes=(1, 64, 1024)):
+    """Launch closures of the prediction for each n_opt in `sizes`, and of the torch route to the same records."""
+    import torch
+    from aircraftoptimalcontrol_amd import _lib, batch
+    from aircraftoptimalcontrol_amd.batch import _ptr, check, lib
+    dev = torch.device("cuda:0")
+    Tg = g["xx_opt"].shape[1]
+    bp = batch.BatchProblem(g["QQt"], g["RRt"], g["QQT"], np.zeros((6, T)), np.zeros((2, T)), float(g["dt"]), device=dev)
+    nz = _lib.MpcNoise(20261016, 0, 0, (C.c_double * 6)(*SIGMA.tolist()))
+    S0 = torch.from_numpy(np.diag((0.1 * DELTA_SCALE) ** 2)[np.triu_indices(6)]).to(dev)
+    runs = {}
+    for n in sizes:
+        off = [(k % max(1, Tg - T + 1)) for k in range(n)]
+        xo = np.stack([g["xx_opt"][:, o:o + T] for o in off])
+        uo = np.stack([g["uu_opt"][:, o:o + T] for o in off])
+        KK = np.stack([g["KK"][:, :, o:o + T] for o in off])
+        nominal = torch.from_numpy(batch.ensemble_nominal(xo, uo, KK)).to(dev)
+        Sig = S0.repeat(n, 1).contiguous()
+        pred = torch.empty((n, T, _lib.AOC_COV_NREC), dtype=torch.float64, device=dev)
+        nbytes = int(lib().aoc_track_covariance_scratch_bytes(n, T))
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        p = bp.c_problem(n)
+
+        def run_P(p=p, n=n, nominal=nominal, Sig=Sig, pred=pred, scratch=scratch, nbytes=nbytes):
+            check(lib().aoc_track_covariance(C.byref(p), n, _ptr(nominal), None, _ptr(Sig), C.byref(nz), _ptr(pred), None,
+                                             _ptr(scratch), nbytes), "aoc_track_covariance")
+
+        # the torch route: one aoc_step_batch over all pairs, then T-1 dependent stages of batched 6x6 products
+        xs = nominal[:, :, 0:6].reshape(-1, 6).contiguous()
+        us = nominal[:, :, 6:8].reshape(-1, 2).contiguous()
+        Kt = nominal[:, :, 8:20].reshape(n, T, 2, 6)
+        xp = torch.empty((n * T, 6), dtype=torch.float64, device=dev)
+        fx = torch.empty((n * T, 6, 6), dtype=torch.float64, device=dev)
+        fu = torch.empty((n * T, 2, 6), dtype=torch.float64, device=dev)
+        W = torch.diag(torch.from_numpy(SIGMA ** 2)).to(dev)
+        iu = torch.triu_indices(6, 6, device=dev)
+        P0 = torch.zeros((n, 6, 6), dtype=torch.float64, device=dev)
+        P0[:, iu[0], iu[1]] = Sig
+        P0 = P0 + P0.transpose(1, 2) - torch.diag_embed(torch.diagonal(P0, dim1=1, dim2=2))
+        out = torch.zeros((n, T, _lib.AOC_COV_NREC), dtype=torch.float64, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+        def run_TQ(n=n, xs=xs, us=us, Kt=Kt, xp=xp, fx=fx, fu=fu, P0=P0, out=out, nominal=nominal):
+            check(lib().aoc_step_batch(C.byref(bp.model), n * T, _ptr(xs), _ptr(us), None, _ptr(xp), _ptr(fx), _ptr(fu), None, None,
+                                       None, st), "aoc_step_batch")
+            A = fx.view(n, T, 6, 6).transpose(2, 3)
+            Bm = fu.view(n, T, 2, 6).transpose(2, 3)
+            F = A + torch.matmul(Bm, Kt)                                                # (n,T,6,6)
+            c = xp.view(n, T, 6)[:, :T - 1] - nominal[:, 1:, 0:6]
+            P, m = P0, torch.zeros((n, 6, 1), dtype=torch.float64, device=dev)
+            for t in range(T):
+                out[:, t, 0:6] = m[:, :, 0]
+                out[:, t, 6:27] = P[:, iu[0], iu[1]]
+                if t == T - 1:
+                    break
+                KP = torch.matmul(Kt[:, t], P)
+                out[:, t, 27:29] = torch.matmul(Kt[:, t], m)[:, :, 0]
+                KPK = torch.matmul(KP, Kt[:, t].transpose(1, 2))
+                out[:, t, 29], out[:, t, 30], out[:, t, 31] = KPK[:, 0, 0], KPK[:, 0, 1], KPK[:, 1, 1]
+                m = torch.matmul(F[:, t], m) + c[:, t].unsqueeze(2)
+                P = torch.matmul(torch.matmul(F[:, t], P), F[:, t].transpose(1, 2)) + W
+            return out
+
+        run_P(); want = run_TQ(); torch.cuda.synchronize()                                # the two routes agree before either is timed
+        scale = want.abs().amax(dim=(0, 1)).clamp(min=1e-300)
+        assert bool((((pred - want).abs() / scale) <= 1e-9).all()), "P and TQ disagree"
+        runs["P_%d" % n], runs["TQ_%d" % n] = run_P, run_TQ
+    return runs
+
+
 def timed(fn, seconds):
     """ms per call over at least `seconds` of back-to-back launches (HIP events; one launch first sizes the window)"""
     import torch
@@ -236,7 +313,7 @@ def kernel_times(d):
     out = collections.OrderedDict()
     for name, t0, t1, grid in sorted(rows, key=lambda r: r[1]):
         name = name.split("(")[0].replace("void ", "").replace("aoc64::", "")
-        if name.startswith(("k_track_", "k_envelope_")):
+        if name.startswith(("k_track_", "k_envelope_", "k_histogram_", "k_cov_")):
             out.setdefault("%s grid=%s" % (name, grid), []).append(round((t1 - t0) / 1e6, 4))
     for k, v in out.items():
         print(json.dumps(dict(kernel=k, ms=v, median=float(np.median(v)), spread_rel=round((max(v) - min(v)) / float(np.median(v)), 4))))
@@ -253,6 +330,7 @@ def main():
     ap.add_argument("--kernel-times", default=None, metavar="DIR", help="summarise the kernel trace(s) under DIR (no GPU)")
     ap.add_argument("--envelope", action="store_true", help="also time the per-sample envelope: E_traj + E_reduce against B_env")
     ap.add_argument("--histogram", action="store_true", help="also time the per-sample histogram: H against B_stats, B_env and Q")
+    ap.add_argument("--predict", action="store_true", help="also time aoc_track_covariance for 1, 64 and 1024 optima")
     ap.add_argument("--hist-valu", type=int, default=0, help="vector instructions per stage of the histogram kernel (from the ISA)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -266,7 +344,11 @@ def main():
     for B in a.members:
         rec = dict(members=B)
         try:
-            runs = setup(B, a.T, g, a.envelope, a.histogram)
+            runs = setup(B, a.T, g, a.envelope, a.histogram or a.predict)
+            if a.predict:
+                if not a.histogram:       # the yardsticks of the prediction only, not the torch routes to the histogram
+                    runs = {k: f for k, f in runs.items() if k in ("A", "B_stats", "B_env", "H")}
+                runs.update(setup_predict(a.T, g))
         except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
             rec["refused"] = "allocation refused: %s" % str(e).split("\n")[0]
             out["sizes"].append(rec)
@@ -289,6 +371,14 @@ def main():
             med = {k: float(np.median(v)) for k, v in ms.items()}
             rec["A_spread_rel"] = round((max(ms["A"]) - min(ms["A"])) / med["A"], 4)
             rec["B_over_A"] = {k: round(med[k] / med["A"], 4) for k in ms if k != "A"}
+            if a.predict:
+                sp = lambda k: round((max(ms[k]) - min(ms[k])) / med[k], 4)
+                rec["predict"] = dict(P_ms={k: med[k] for k in med if k.startswith("P_")},
+                                      TQ_ms={k: med[k] for k in med if k.startswith("TQ_")},
+                                      C_ms=med["B_stats"], E_ms=med["B_env"], H_ms=med["H"],
+                                      P1_over_C=round(med["P_1"] / med["B_stats"], 4),
+                                      two_pass_ms=round(med["B_env"] + med["H"], 4), one_pass_ms=round(med["P_1"] + med["H"], 4),
+                                      spread_rel={k: sp(k) for k in ("P_1", "P_64", "P_1024", "B_stats", "B_env", "H")})
             if a.envelope:
                 E = med["E_traj"] + med["E_reduce"]
                 rec["envelope"] = dict(E_ms=round(E, 4), B_env_over_E=round(med["B_env"] / E, 4),
