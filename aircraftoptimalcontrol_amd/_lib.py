@@ -18,6 +18,7 @@ AOC_ENS_NSTAT = 16   # statistics per member of aoc_track_ensemble
 AOC_ENV_NREC = 44    # doubles per (optimum, sample) record of aoc_track_ensemble_envelope
 AOC_HIST_NCH, AOC_HIST_NBIN = 8, 64   # channels (dx[0..5], du[0..1]) and bins per channel of aoc_track_ensemble_histogram
 AOC_COV_NREC = 32    # doubles per (optimum, sample) record of aoc_track_covariance
+AOC_LQG_NSTAT = 12   # estimation-error statistics per member of aoc_track_ensemble_lqg
 AOC_ABI_VERSION = 5   # include/aoc.h: the revision this binding (struct layouts, argument lists) is written against
 
 # status flags (include/aoc.h)
@@ -128,6 +129,8 @@ SYMBOLS = {
     "aoc_track_ensemble_histogram": (C.c_int, [_P, _I, _I] + [_P] * 11 + [_Z]),
     "aoc_track_covariance_scratch_bytes": (_Z, [_I, _I]),
     "aoc_track_covariance": (C.c_int, [_P, _I] + [_P] * 7 + [_Z]),
+    "aoc_track_ensemble_lqg_scratch_bytes": (_Z, [_I, _I]),
+    "aoc_track_ensemble_lqg": (C.c_int, [_P, _I, _I] + [_P] * 15 + [_Z]),
     "aoc_traj_cost_f32": (C.c_int, [_P] * 5),
     "aoc_initial_trajectory_f32": (C.c_int, [_P, _D, _D, _P, _P, _P]),
     "aoc_rollout_cost_f32": (C.c_int, [_P] * 9),

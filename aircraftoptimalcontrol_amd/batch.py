@@ -986,6 +986,7 @@ ENV_NREC = _lib.AOC_ENV_NREC       # doubles per (optimum, sample) record of aoc
 HIST_NCH = _lib.AOC_HIST_NCH       # channels of aoc_track_ensemble_histogram: dx[0..5], du[0..1]
 HIST_NBIN = _lib.AOC_HIST_NBIN     # bins per (optimum, sample, channel)
 COV_NREC = _lib.AOC_COV_NREC       # doubles per (optimum, sample) record of aoc_track_covariance
+LQG_NSTAT = _lib.AOC_LQG_NSTAT     # estimation-error statistics per member of aoc_track_ensemble_lqg
 # the record (include/aoc.h): n | min dx | max dx | min du | max du | sum dx | sum dx_i dx_j (upper triangle, row by row)
 _ENV_MIN = np.r_[1:7, 13:15]
 _ENV_MAX = np.r_[7:13, 15:17]
@@ -1247,6 +1248,47 @@ def predict_covariance(problem, xx_opt, uu_opt, KK=None, mean0=None, Sigma0=None
     return [_covariance_dict(r) for r in raw], status
 
 
+def filter_gains(problem, xx_opt, uu_opt, Sigma0, sigma, rho, jac=None):
+    """Gains of the Kalman filter linearised about ONE optimum, for track_ensemble(rho=, filter=): the recursion in NumPy,
+        L_t = P^-_t (P^-_t + V)^-1,   P^+_t = (I - L_t) P^-_t (I - L_t)^T + L_t V L_t^T   (Joseph form),
+        P^-_{t+1} = A_t P^+_t A_t^T + W,      P^-_0 = Sigma0,  W = diag(sigma^2),  V = diag(rho^2),
+    for the measurement y = dx + v of the whole deviation.  xx_opt (6,T), uu_opt (2,T); Sigma0 (6,6) the covariance of the
+    prior estimate's error at sample 0; sigma (6,) the std of the disturbance (None = 0), rho (6,) that of the measurement
+    noise, every component > 0.  A_t (and B_t, unused by a filter that knows its input) are the Jacobians of Dynamics.step
+    along the optimum: from step_batch on the device, or jac=(A (T-1,6,6), B (T-1,6,2)) as given (the oracle's, where no
+    GPU is at hand).  Returns L (6,6,T), P_prior (6,6,T), P_post (6,6,T)."""
+    xo, uo = np.asarray(xx_opt, dtype=np.float64), np.asarray(uu_opt, dtype=np.float64)
+    T = xo.shape[1]
+    if xo.shape != (6, T) or uo.shape != (2, T):
+        raise ValueError("xx_opt (6,T) and uu_opt (2,T) expected, got %s %s" % (xo.shape, uo.shape))
+    rho = np.asarray(rho, dtype=np.float64)
+    if rho.shape != (6,) or not np.all(np.isfinite(rho) & (rho > 0)):
+        raise ValueError("rho must be six finite standard deviations > 0, got %s" % (rho,))
+    W = np.zeros((6, 6)) if sigma is None else np.diag(np.asarray(sigma, dtype=np.float64) ** 2)
+    V = np.diag(rho ** 2)
+    P = np.asarray(Sigma0, dtype=np.float64)
+    if P.shape != (6, 6) or not np.array_equal(P, P.T):
+        raise ValueError("Sigma0 must be a symmetric (6,6) matrix")
+    if jac is None:
+        _, fx, _, _, _, _ = step_batch(problem.model, xo[:, :T - 1].T, uo[:, :T - 1].T, device=problem.device)
+        A = fx.transpose(0, 2, 1)                                 # aoc_step_batch: fx = A^T
+    else:
+        A = np.asarray(jac[0], dtype=np.float64)
+    if A.shape != (T - 1, 6, 6):
+        raise ValueError("A must be (T-1,6,6) = %s, got %s" % ((T - 1, 6, 6), A.shape))
+    L, Pm, Pp = np.zeros((6, 6, T)), np.zeros((6, 6, T)), np.zeros((6, 6, T))
+    I = np.eye(6)
+    for t in range(T):
+        Lt = np.linalg.solve(P + V, P).T                          # P (P + V)^-1, both symmetric
+        post = (I - Lt) @ P @ (I - Lt).T + Lt @ V @ Lt.T
+        post = 0.5 * (post + post.T)
+        L[:, :, t], Pm[:, :, t], Pp[:, :, t] = Lt, P, post
+        if t < T - 1:
+            P = A[t] @ post @ A[t].T + W
+            P = 0.5 * (P + P.T)
+    return L, Pm, Pp
+
+
 def _ens_summary(torch, v):
     """mean / max / quantiles over the members (rows) of one optimum, reduced on the device"""
     q = torch.quantile(v, torch.tensor(ENS_QUANTILES, dtype=v.dtype, device=v.device), dim=0)
@@ -1257,7 +1299,8 @@ def _ens_summary(torch, v):
 
 def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, sigma=None, seed=20260405, first=0,
                    step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True, envelope=False,
-                   quantiles=None, bins=None, predict=False, mean0=None, Sigma0=None, predict_k=6.0):
+                   quantiles=None, bins=None, predict=False, mean0=None, Sigma0=None, predict_k=6.0, rho=None, filter=None,
+                   ehat0=None):
     """Closed-loop tracking ensemble about shared optima (aoc_track_ensemble): the loop of lqr_tracking.py:279-281 for B
     members, u_t = u_opt_t + K_t (x_t - x_opt_t), x_{t+1} = step(x_t, u_t) + d_t, reduced to per-member statistics on
     the device; the optimum and its gains are stored once per optimum, not once per member.
@@ -1291,7 +1334,20 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     on the host.  The disturbance is the call's own sigma.
     bins="predicted" (with quantiles=): the bins are histogram_bins_predicted of that prediction, mean -+ predict_k std, so
     the histogram call is the ONLY pass over the members — no envelope call unless envelope=True asks for it — and
-    `predicted` is returned as well."""
+    `predicted` is returned as well.
+    filter=L (6,6,T) or (n_opt,6,6,T) (aoc_track_ensemble_lqg; filter_gains computes such gains): no member feeds back its
+    true state but a Kalman estimate from noisy measurements, y_t = dx_t + v_t, e^+_t = e^-_t + L_t (y_t - e^-_t),
+    u_t = u_opt_t + K_t e^+_t, e^-_{t+1} = F_t e^+_t + c_t (include/aoc.h).  rho (6,) or None: std of the measurement noise
+    v_t, drawn on the device — mpc.noise_draws(seed, step0 + t, first, B, rho, 1) restates it —; None: v = 0.  ehat0 (6,) or
+    (n_opt,6): the prior estimate of dx_0 of each optimum's members, None = 0.  Every output above is then that of this
+    loop; added: est_stats (B,12), max_e (B,6) = max_t |e_t| and sum_e2 (B,6) = sum_t e_t^2 of the estimation error e_t =
+    dx_t - e^+_t, and with trajectories=True xhat (B,6,T) = x_opt_t + e^+_t and meas (B,6,T) = v_t.  rho= or ehat0= without
+    filter=, and filter= together with envelope=, quantiles= or predict=, raise ValueError."""
+    lqg = filter is not None
+    if not lqg and (rho is not None or ehat0 is not None):
+        raise ValueError("rho= and ehat0= go with filter= (the gains of the estimator, e.g. from filter_gains)")
+    if lqg and (envelope or quantiles is not None or predict or bins is not None):
+        raise ValueError("filter= (the estimator in the loop) does not combine with envelope=, quantiles= or predict=")
     torch = _torch()
     dev = problem.device
     xo, uo = np.asarray(xx_opt, dtype=np.float64), np.asarray(uu_opt, dtype=np.float64)
@@ -1381,7 +1437,36 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
                                                  _ptr(hist_d), _ptr(scratch) if nbytes else None, nbytes),
               "aoc_track_ensemble_histogram")
         del scratch
-    if not envelope and not hist:
+    if lqg:
+        Lf = np.asarray(filter, dtype=np.float64)
+        Lf = Lf[None] if Lf.ndim == 3 else Lf
+        if Lf.shape != (n_opt, 6, 6, T):
+            raise ValueError("filter must be (6,6,T) or (n_opt,6,6,T) = %s, got %s" % ((n_opt, 6, 6, T), Lf.shape))
+        filt_d = torch.from_numpy(np.ascontiguousarray(Lf.reshape(n_opt, 36, T).transpose(0, 2, 1))).to(dev)   # [opt][t][36]
+        e0_d = None
+        if ehat0 is not None:
+            e0 = np.asarray(ehat0, dtype=np.float64)
+            e0 = np.broadcast_to(e0, (n_opt, 6)) if e0.ndim == 1 else e0
+            if e0.shape != (n_opt, 6):
+                raise ValueError("ehat0 must be (6,) or (n_opt,6) with n_opt = %d, got %s" % (n_opt, e0.shape))
+            e0_d = _dev_f64(np.ascontiguousarray(e0), dev)
+        rho_c = None
+        if rho is not None:
+            rho_c = (C.c_double * 6)(*np.asarray(rho, dtype=np.float64).reshape(6).tolist())
+            if nz is None:                                      # the seed lives in the disturbance model: one that adds nothing
+                nz = _lib.MpcNoise(int(seed), int(step0), int(first), (C.c_double * 6)(*([0.0] * 6)))
+                nzp = C.byref(nz)
+        est_stats = torch.empty((nt, LQG_NSTAT, TILE), dtype=torch.float64, device=dev)
+        xh = ms = None
+        if trajectories:
+            xh, ms = alloc_tiled(B, T, 6, dev), alloc_tiled(B, T, 6, dev)
+        nbytes = int(lib().aoc_track_ensemble_lqg_scratch_bytes(n_opt, T))
+        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+        check(lib().aoc_track_ensemble_lqg(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(filt_d), _ptr(x0t), _ptr(e0_d), nzp, rho_c,
+                                           _ptr(xr), _ptr(ur), _ptr(xh), _ptr(ds), _ptr(ms), _ptr(stats), _ptr(est_stats),
+                                           _ptr(status), _ptr(scratch), nbytes), "aoc_track_ensemble_lqg")
+        del scratch
+    elif not envelope and not hist:
         check(lib().aoc_track_ensemble(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp,
                                        _ptr(xr), _ptr(ur), _ptr(ds), _ptr(stats), _ptr(status)), "aoc_track_ensemble")
     sv = unpack_vec(stats, B)                                   # (B,16) on the device
@@ -1395,6 +1480,9 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     s = sv.cpu().numpy()
     out = dict(max_dx=s[:, 0:6], max_du=s[:, 6:8], cost=s[:, 8], final_dx=s[:, 9:15], first_bad=s[:, 15].astype(np.int64),
                status=status[:B].cpu().numpy(), stats=s, members_per_opt=mpo, group=group, summary=summary)
+    if lqg:
+        es = unpack_vec(est_stats, B).cpu().numpy()
+        out.update(est_stats=es, max_e=es[:, 0:6], sum_e2=es[:, 6:12])
     if envelope:
         out["envelope"] = [_envelope_dict(r) for r in env.cpu().numpy()]
     if predict:
@@ -1409,6 +1497,8 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
         xd[:, :, 0] = _dev_f64(x0, dev)                         # sample 0 is the fp64 x0, as everywhere
         host = (lambda t: t.cpu().numpy()) if to_host else (lambda t: t)
         out.update(xx_reg=host(xd), uu_reg=host(unpack(ur, B)), dist=host(unpack(ds, B)))
+        if lqg:
+            out.update(xhat=host(unpack(xh, B)), meas=host(unpack(ms, B)))
     return out
 
 

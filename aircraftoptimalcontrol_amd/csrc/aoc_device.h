@@ -601,12 +601,13 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-// the six disturbance components of global instance `inst` at the step of `nz`
-__device__ __forceinline__ void mpc_noise_draw(const MpcNoise& nz, unsigned inst, double d[6]) {
+// the six disturbance components of global instance `inst` at the step of `nz`; `stream` is the counter's fourth word: 0 the
+// disturbance, 1 the measurement noise of the estimator instances of k_track_ensemble — streams that never share a counter
+__device__ __forceinline__ void mpc_noise_draw(const MpcNoise& nz, unsigned inst, double d[6], unsigned stream = 0u) {
 #pragma unroll
     for (int j = 0; j < 3; j++) {
         unsigned w[4];
-        philox4x32_10(inst, nz.step, (unsigned)j, 0u, nz.key0, nz.key1, w);
+        philox4x32_10(inst, nz.step, (unsigned)j, stream, nz.key0, nz.key1, w);
         // 53-bit uniforms in (0, 1]: (27 high bits of one word, 26 of the next) + 1, times 2^-53
         const double u1 = ((double)(w[0] >> 5) * 67108864.0 + (double)(w[1] >> 6) + 1.0) * 0x1.0p-53;
         const double u2 = ((double)(w[2] >> 5) * 67108864.0 + (double)(w[3] >> 6) + 1.0) * 0x1.0p-53;

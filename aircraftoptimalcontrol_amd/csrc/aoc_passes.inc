@@ -22,5 +22,6 @@ namespace AOC_ARITH_NS {
 #endif  // AOC_KERNELS_ONLY
 #include "passes/ensemble.inc"   // kernel and launch function in one file (the latter uses make_const of api.inc)
 #include "passes/covariance.inc" // likewise (the nominal's record is that of ensemble.inc)
+#include "passes/lqg.inc"        // launch function only: k_cov_stage of covariance.inc, then the EST instance of ensemble.inc
 
 }  // namespace AOC_ARITH_NS

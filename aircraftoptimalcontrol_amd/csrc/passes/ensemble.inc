@@ -92,6 +92,47 @@ static_assert(HIST_PF * TILE == ENS_BLK * HIST_REC, "a block of bins is a whole 
 static_assert(HIST_DRAIN * TILE * 4 == HIST_S * HIST_DW, "a drain is a whole number of 16-byte pieces per lane");
 static_assert(TILE <= 255, "a tile's count fits a byte");
 
+// ---- noisy measurements and a Kalman estimate in the loop (aoc_track_ensemble_lqg) ------------------------------------------
+// The EST instances of k_track_ensemble feed back an estimate instead of the true deviation.  With dx_t = x_t - x_opt_t, the
+// measurement y_t = dx_t + v_t and e^-_0 = ehat0 of the optimum, sample t = 0 .. T-1 does
+//     e^+_t = e^-_t + L_t (y_t - e^-_t),      u_t = u_opt_t + K_t e^+_t,      e^-_{t+1} = F_t e^+_t + c_t      (t <= T-2),
+// F_t = A_t + B_t K_t and c_t the records of k_cov_stage (covariance.inc; launched into the call's scratch by lqg.inc), L_t
+// the caller's filter gains: all three depend on the optimum only, so they reach the lanes through LDS like the nominal —
+// EST_FC_PF + EST_L_PF coalesced doubles per lane and block of ENS_BLK stages (block b = the records of the SAME stages
+// b*ENS_BLK ..), read back with every lane at one address.  The whole record of k_cov_stage is staged as it lies (a
+// contiguous stream; its copy of K and its status word are not read).  Unlike the nominal this block is NOT prefetched
+// through registers and NOT double-buffered: 23 doubles per lane held over a block of stages are 46 VGPRs on top of instances
+// that already fill the register file (the first form spilled to private scratch), and a stage takes 1500-5000 cycles
+// against one exposed load (an L2 hit: every tile of the optimum reads the same records) per sixteen stages.  So the block is loaded and written between two blocks of
+// stages: 16 x (56 + 36) doubles = 11.5 KB beside the nominal's 5 KB.
+// The estimate is six registers per lane.  L (y - e^-) and F e^+ are chains of fused multiply-adds from +0.0 in index order,
+// added to e^- resp. c once: with L = 0 and c = 0 the estimate stays exactly +0.0.  v_t[c] = rho[c] z from the generator of
+// the disturbance with the counter's fourth word 1 (mpc_noise_draw), drawn only where rho draws, else +0.0.
+// est_stats[tile][EST_NSTAT][64]: 0-5 max_t |e_t[c]| of e_t = dx_t - e^+_t (a NaN sticks), 6-11 sum_t e_t[c]^2 in sample order.
+constexpr int EST_FC = 56;      // doubles per sample of the F / c records (COV_REC, asserted in lqg.inc) ...
+constexpr int EST_O_C = 36;     // ... and where c starts in one (COV_O_C)
+constexpr int EST_L = 36;       // doubles per sample of `filter`
+constexpr int EST_NSTAT = 12;   // AOC_LQG_NSTAT
+constexpr int EST_FC_PF = ENS_BLK * EST_FC / TILE, EST_L_PF = ENS_BLK * EST_L / TILE;   // doubles per lane and block
+static_assert(EST_FC_PF * TILE == ENS_BLK * EST_FC && EST_L_PF * TILE == ENS_BLK * EST_L,
+              "a block of estimator records is a whole number of doubles per lane");
+static_assert(EST_FC % 2 == 0 && EST_O_C % 2 == 0 && EST_L % 2 == 0, "rows of F, c and L start on 16 bytes");
+
+// what the EST instances take beside the arguments of every instance (nothing otherwise: the other instances' arguments
+// are what they were)
+template <bool EST>
+struct EnsEst {};
+template <>
+struct EnsEst<true> {
+    const real* fc;        // [opt][T][EST_FC]
+    const real* filter;    // [opt][T][EST_L]
+    const real* ehat0;     // [opt][6] or NULL
+    MpcNoise mz;           // the measurement noise: sigma = rho, on = whether rho draws
+    real* xhat_reg;        // tiled C=6 or NULL
+    real* meas_out;        // tiled C=6 or NULL
+    real* est_stats;       // [tile][EST_NSTAT][64]
+};
+
 // max over |v| with a NaN that sticks (fmax would drop it): for non-negative doubles the IEEE order is the order of
 // the bit patterns as unsigned integers, and every NaN lies above +inf there
 __device__ __forceinline__ void ens_absmax(unsigned long long& m, double v) {
@@ -108,19 +149,23 @@ __device__ __forceinline__ bool ens_finite6(const real x[6]) {
 // (first + member, step + t, c / 2, 0); the stats-only, noise-free instance carries neither stores nor the generator.
 // ENV: also the per-tile envelope records part[tile][t][ENV_NREC] (above); every other output keeps its bits.
 // HIST: also the per-tile byte counts part[tile][t][HIST_NCH][HIST_NBIN] under `bins` (above); never together with ENV.
-template <bool WRITE, bool NOISE, typename XO, bool DIAG, bool ENV = false, bool HIST = false>
+// EST: the input is fed back from the estimate of `est` (above) instead of the true deviation; never with ENV or HIST.
+template <bool WRITE, bool NOISE, typename XO, bool DIAG, bool ENV = false, bool HIST = false, bool EST = false>
 __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_per_opt, const real* __restrict__ nominal,
                                                          const real* __restrict__ x0, MpcNoise nz, XO* __restrict__ x_reg,
                                                          real* __restrict__ u_reg, real* __restrict__ dist_out,
                                                          real* __restrict__ stats, int* __restrict__ status,
                                                          real* __restrict__ part = nullptr,
-                                                         const real* __restrict__ bins = nullptr) {
+                                                         const real* __restrict__ bins = nullptr, EnsEst<EST> est = {}) {
 #pragma clang fp contract(off)
     static_assert(!(ENV && HIST), "the bins come from an envelope call: the two are never one instance");
+    static_assert(!(EST && (ENV || HIST)), "the estimator instances reduce nothing over the members");
     __shared__ __attribute__((aligned(16))) real sh[2][ENS_BLK * ENS_REC];
     __shared__ __attribute__((aligned(16))) real ev[ENV ? ENV_S * ENV_ROWS * ENV_LD : 2];
     __shared__ __attribute__((aligned(16))) real hb[HIST ? 2 * ENS_BLK * HIST_REC : 2];
     __shared__ __attribute__((aligned(16))) unsigned hc[HIST ? HIST_S * HIST_DW : 4];
+    __shared__ __attribute__((aligned(16))) real ef[EST ? ENS_BLK * EST_FC : 2];
+    __shared__ __attribute__((aligned(16))) real el[EST ? ENS_BLK * EST_L : 2];
     // uniform constants in VGPRs (aoc_device.h pin_consts) where the SGPRs do not hold them: the diagonal weights (dense
     // ones are re-loaded from the kernel arguments inside the stage), and beside the generator's constants the model too
     KConst k = kc;
@@ -134,6 +179,9 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
     real xs[6], xn[6], cur[ENS_REC], q[6], r[2], pf[ENS_PF], hpf[HIST ? HIST_PF : 1];
     const real* __restrict__ bin = HIST ? bins + (size_t)(tile / tiles_per_opt) * T * HIST_REC : nullptr;   // wave-uniform
     const size_t nbin = (size_t)T * HIST_REC;
+    real eh[6], se[6];
+    unsigned long long me[6] = {0, 0, 0, 0, 0, 0};
+    const size_t nfc = (size_t)T * EST_FC, nfl = (size_t)T * EST_L;
     // block b of the nominal = records b*ENS_BLK + 1 .. (b+1)*ENS_BLK (what the stages b*ENS_BLK .. read AHEAD), one
     // coalesced load of ENS_PF doubles per lane; indices beyond the last record are clamped onto it
     auto fetch = [&](int b) {
@@ -156,6 +204,30 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
         if (HIST) {
 #pragma unroll
             for (int i = 0; i < HIST_PF; i++) hb[(b & 1) * ENS_BLK * HIST_REC + i * TILE + lane] = hpf[i];
+        }
+        // block b of F / c and of L = the records b*ENS_BLK .. (b+1)*ENS_BLK - 1 (clamped likewise) replaces block b - 1, HERE,
+        // between two blocks of stages and not through registers held over a block — unless no sample up to T-1 is in it
+        // (then sample T-1 still reads block b - 1)
+        if constexpr (EST) {
+            if (b * ENS_BLK <= T - 1) {
+                const real* __restrict__ fc = est.fc + (size_t)(tile / tiles_per_opt) * nfc;       // wave-uniform
+                const real* __restrict__ fl = est.filter + (size_t)(tile / tiles_per_opt) * nfl;
+                real fpf[EST_FC_PF], lpf[EST_L_PF];
+#pragma unroll
+                for (int i = 0; i < EST_FC_PF; i++) {
+                    const size_t e = (size_t)b * ENS_BLK * EST_FC + i * TILE + lane;
+                    fpf[i] = fc[e < nfc ? e : nfc - 1];
+                }
+#pragma unroll
+                for (int i = 0; i < EST_L_PF; i++) {
+                    const size_t e = (size_t)b * ENS_BLK * EST_L + i * TILE + lane;
+                    lpf[i] = fl[e < nfl ? e : nfl - 1];
+                }
+#pragma unroll
+                for (int i = 0; i < EST_FC_PF; i++) ef[i * TILE + lane] = fpf[i];
+#pragma unroll
+                for (int i = 0; i < EST_L_PF; i++) el[i * TILE + lane] = lpf[i];
+            }
         }
         __syncthreads();   // one wavefront: orders the LDS writes before the broadcast reads, costs nothing
     };
@@ -258,6 +330,63 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
 #pragma unroll
         for (int i = 0; i < HIST_DRAIN; i++) pc[i * TILE + lane] = make_uint4(0u, 0u, 0u, 0u);
     }
+    // estimator: sample t of this member: the measurement of dx, e^+ = e^- + L_t (y - e^-) into ep, the error statistics,
+    // and x_opt_t + e^+ (xo = the record of the nominal) and v_t for a checker
+    auto est_update = [&](int t, const real dx[6], const real* xo, real ep[6]) {
+        if constexpr (EST) {
+            __builtin_amdgcn_sched_barrier(0);   // the reads of L stay here (they are not worth 72 registers held earlier)
+            real v[6], nu[6];
+#pragma unroll
+            for (int c = 0; c < 6; c++) v[c] = R(0.0);
+            if (NOISE && est.mz.on) {
+                MpcNoise mt = est.mz;
+                mt.step = est.mz.step + (unsigned)t;
+                double dn[6];
+                mpc_noise_draw(mt, est.mz.first + (unsigned)member, dn, 1u);
+#pragma unroll
+                for (int c = 0; c < 6; c++) v[c] = (real)dn[c];
+            }
+#pragma unroll
+            for (int c = 0; c < 6; c++) nu[c] = (dx[c] + v[c]) - eh[c];
+            const real2v* __restrict__ Lr = (const real2v*)&el[(t % ENS_BLK) * EST_L];
+#pragma unroll
+            for (int i = 0; i < 6; i++) {   // every lane the same address: a broadcast
+                const real2v l0 = Lr[3 * i], l1 = Lr[3 * i + 1], l2 = Lr[3 * i + 2];
+                real s = __builtin_fma(l0.y, nu[1], __builtin_fma(l0.x, nu[0], R(0.0)));
+                s = __builtin_fma(l1.y, nu[3], __builtin_fma(l1.x, nu[2], s));
+                s = __builtin_fma(l2.y, nu[5], __builtin_fma(l2.x, nu[4], s));
+                ep[i] = eh[i] + s;
+                const real e = dx[i] - ep[i];
+                ens_absmax(me[i], e);
+                se[i] = se[i] + e * e;
+                if (WRITE && est.xhat_reg) st_stream(&est.xhat_reg[tix<6>(tile, T, t, i, lane)], xo[i] + ep[i]);
+                if (WRITE && est.meas_out) st_stream(&est.meas_out[tix<6>(tile, T, t, i, lane)], v[i]);
+            }
+        }
+    };
+    // e^-_{t+1} = F_t e^+_t + c_t
+    auto est_predict = [&](int t, const real ep[6]) {
+        if constexpr (EST) {
+            __builtin_amdgcn_sched_barrier(0);   // likewise the reads of F and c
+            const real2v* __restrict__ Fr = (const real2v*)&ef[(t % ENS_BLK) * EST_FC];
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                const real2v f0 = Fr[3 * i], f1 = Fr[3 * i + 1], f2 = Fr[3 * i + 2], cc = Fr[EST_O_C / 2 + i / 2];
+                real s = __builtin_fma(f0.y, ep[1], __builtin_fma(f0.x, ep[0], R(0.0)));
+                s = __builtin_fma(f1.y, ep[3], __builtin_fma(f1.x, ep[2], s));
+                s = __builtin_fma(f2.y, ep[5], __builtin_fma(f2.x, ep[4], s));
+                eh[i] = s + ((i & 1) ? cc.y : cc.x);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    if constexpr (EST) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            eh[c] = est.ehat0 ? est.ehat0[(size_t)(tile / tiles_per_opt) * 6 + c] : R(0.0);
+            se[c] = R(0.0);
+        }
+    }
     unsigned long long mx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     real JJ = R(0.0);
     int flags = 0, first_bad = T;
@@ -275,16 +404,20 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
       const int n = T - 1 - t0 < ENS_BLK ? T - 1 - t0 : ENS_BLK;
       for (int i = 0; i < n; i++) {
         const int t = t0 + i;
-        real d[6], u0, u1;
-        // uu_reg = uu_opt + KK @ (xx_reg - xx_opt)   (lqr_tracking.py:280), summed from 0 in index order
+        real d[6], ep[6], u0, u1;
+        // uu_reg = uu_opt + KK @ (xx_reg - xx_opt)   (lqr_tracking.py:280), summed from 0 in index order; EST: K times the
+        // estimate of the deviation instead
 #pragma unroll
         for (int c = 0; c < 6; c++) d[c] = xs[c] - cur[c];
+        est_update(t, d, cur, ep);
         real a0 = R(0.0), a1 = R(0.0);
 #pragma unroll
         for (int c = 0; c < 6; c++) {
-            a0 += cur[8 + c] * d[c];
-            a1 += cur[14 + c] * d[c];
+            const real fb = EST ? ep[c] : d[c];
+            a0 += cur[8 + c] * fb;
+            a1 += cur[14 + c] * fb;
         }
+        est_predict(t, ep);
         u0 = cur[6] + a0;
         u1 = cur[7] + a1;
         const bool vbad = !(xs[2] > R(0.0)), nonfin = !ens_finite6(xs);
@@ -344,6 +477,8 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
         dT[c] = xs[c] - cur[c];
         ens_absmax(mx[c], dT[c]);
     }
+    real epT[6];
+    est_update(T - 1, dT, cur, epT);
     const bool nonfin = !ens_finite6(xs);
     if (nonfin) flags |= AOC_ST_NAN;
     if ((nonfin || !(xs[2] > R(0.0))) && T - 1 < first_bad) first_bad = T - 1;
@@ -372,6 +507,14 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
     for (int c = 0; c < 6; c++) so[(9 + c) * TILE] = dT[c];
     so[15 * TILE] = (real)first_bad;
     if (status && flags) status[tile * TILE + lane] |= flags;
+    if constexpr (EST) {
+        real* __restrict__ eo = est.est_stats + (size_t)tile * EST_NSTAT * TILE + lane;
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            eo[c * TILE] = (real)__longlong_as_double((long long)me[c]);
+            eo[(6 + c) * TILE] = se[c];
+        }
+    }
 }
 
 // envelope[opt][t][q] from part[tile][t][q]: the tiles of an optimum folded in tile order, one thread per number (a sum for
@@ -450,23 +593,16 @@ static size_t ensemble_histogram_scratch_bytes(int32_t B, int32_t T, int32_t mem
 
 enum { ENS_PLAIN = 0, ENS_ENVELOPE = 1, ENS_HISTOGRAM = 2 };
 
-// Body of aoc_track_ensemble, (mode ENS_ENVELOPE: with envelope, scratch, scratch_bytes) of aoc_track_ensemble_envelope and
-// (mode ENS_HISTOGRAM: with bins, hist, scratch, scratch_bytes) of aoc_track_ensemble_histogram, fn the name
-// of the entry point for the reasons.  A template only so that the kernels it names are instantiated where it is called
-// — from the fp64 entry points — and not once more in the float32 namespace.
-template <typename = void>
-static int api_track_ensemble(const char* fn, int mode, const aoc_problem* p, int32_t n_opt, int32_t members_per_opt,
-                              const real* nominal, const real* x0_reg, const aoc_mpc_noise* noise, void* x_reg, real* u_reg,
-                              real* dist_out, real* stats, int32_t* status, real* envelope, const real* bins, int32_t* hist,
-                              void* scratch, size_t scratch_bytes) {
-    const bool env = mode == ENS_ENVELOPE, hst = mode == ENS_HISTOGRAM;
+// The refusals every ensemble call shares (aoc_track_ensemble and what builds on it, lqg.inc included), in the order they are
+// reported; `missing` names a further argument of the caller's that is NULL and must not be (or is nullptr).
+static int ens_check_args(const char* fn, const aoc_problem* p, int32_t n_opt, int32_t members_per_opt, const real* nominal,
+                          const real* x0_reg, const aoc_mpc_noise* noise, const void* x_reg, const real* u_reg,
+                          const real* stats, const char* missing) {
     if (!p) return einval("%s: aoc_problem is NULL", fn);
     if (!nominal) return einval("%s: nominal is NULL", fn);
     if (!x0_reg) return einval("%s: x0_reg is NULL", fn);
     if (!stats) return einval("%s: stats is NULL", fn);
-    if (env && !envelope) return einval("%s: envelope is NULL", fn);
-    if (hst && !bins) return einval("%s: bins is NULL", fn);
-    if (hst && !hist) return einval("%s: hist is NULL", fn);
+    if (missing) return einval("%s: %s is NULL", fn, missing);
     if (n_opt < 1) return einval("%s: n_opt = %d (need n_opt >= 1)", fn, n_opt);
     if (members_per_opt < TILE || members_per_opt % TILE)
         return einval("%s: members_per_opt = %d is not a positive multiple of %d", fn, members_per_opt, TILE);
@@ -481,6 +617,34 @@ static int api_track_ensemble(const char* fn, int mode, const aoc_problem* p, in
                       "x_reg must be fp64", fn);
     if (p->RRt[1] != p->RRt[2])
         return einval("%s: aoc_problem.RRt is not symmetric (R01 = %g, R10 = %g)", fn, p->RRt[1], p->RRt[2]);
+    return AOC_OK;
+}
+
+// the kernels' form of the caller's disturbance model (NULL: none, on = 0)
+static MpcNoise ens_noise(const aoc_mpc_noise* noise) {
+    MpcNoise nz;
+    memset(&nz, 0, sizeof nz);
+    if (noise) {
+        nz.key0 = (unsigned)(noise->seed & 0xffffffffull); nz.key1 = (unsigned)(noise->seed >> 32);
+        nz.step = noise->step; nz.first = noise->first;
+        for (int c = 0; c < 6; c++) nz.sigma[c] = noise->sigma[c];
+        nz.on = 1;
+    }
+    return nz;
+}
+
+// Body of aoc_track_ensemble, (mode ENS_ENVELOPE: with envelope, scratch, scratch_bytes) of aoc_track_ensemble_envelope and
+// (mode ENS_HISTOGRAM: with bins, hist, scratch, scratch_bytes) of aoc_track_ensemble_histogram, fn the name
+// of the entry point for the reasons.  A template only so that the kernels it names are instantiated where it is called
+// — from the fp64 entry points — and not once more in the float32 namespace.
+template <typename = void>
+static int api_track_ensemble(const char* fn, int mode, const aoc_problem* p, int32_t n_opt, int32_t members_per_opt,
+                              const real* nominal, const real* x0_reg, const aoc_mpc_noise* noise, void* x_reg, real* u_reg,
+                              real* dist_out, real* stats, int32_t* status, real* envelope, const real* bins, int32_t* hist,
+                              void* scratch, size_t scratch_bytes) {
+    const bool env = mode == ENS_ENVELOPE, hst = mode == ENS_HISTOGRAM;
+    const char* missing = env && !envelope ? "envelope" : (hst && !bins ? "bins" : (hst && !hist ? "hist" : nullptr));
+    if (int rc = ens_check_args(fn, p, n_opt, members_per_opt, nominal, x0_reg, noise, x_reg, u_reg, stats, missing)) return rc;
     if (env) {
         const size_t need = ensemble_envelope_scratch_bytes(p->B, p->T, members_per_opt);
         if (!scratch) return einval("%s: scratch is NULL (need %zu bytes, aoc_ensemble_envelope_scratch_bytes)", fn, need);
@@ -496,14 +660,7 @@ static int api_track_ensemble(const char* fn, int mode, const aoc_problem* p, in
             return einval("%s: scratch and hist must be 16-byte aligned", fn);
     }
     KConst k = make_const(p->model, p->QQt, p->RRt, p->QQT, p->B, p->T);
-    MpcNoise nz;
-    memset(&nz, 0, sizeof nz);
-    if (noise) {
-        nz.key0 = (unsigned)(noise->seed & 0xffffffffull); nz.key1 = (unsigned)(noise->seed >> 32);
-        nz.step = noise->step; nz.first = noise->first;
-        for (int c = 0; c < 6; c++) nz.sigma[c] = noise->sigma[c];
-        nz.on = 1;
-    }
+    const MpcNoise nz = ens_noise(noise);
     hipStream_t st = (hipStream_t)p->stream;
     const int tpo = members_per_opt / TILE;
     const bool write = x_reg || dist_out;

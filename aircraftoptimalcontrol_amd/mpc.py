@@ -43,14 +43,16 @@ def philox4x32_10(c0, c1, c2, c3, k0, k1):
     return c0, c1, c2, c3
 
 
-def noise_draws(seed, step, first, B, sigma):
+def noise_draws(seed, step, first, B, sigma, word3=0):
     """(B,6) disturbance of closed-loop step `step` for the global instances first .. first+B-1: what the device draws
-    (csrc/aoc_device.h mpc_noise_draw), restated with NumPy's log / sqrt / sin / cos (agreement ~1e-16 of sigma)."""
+    (csrc/aoc_device.h mpc_noise_draw), restated with NumPy's log / sqrt / sin / cos (agreement ~1e-16 of sigma).
+    word3: the counter's fourth word, 0 for the disturbance, 1 for the measurement noise of aoc_track_ensemble_lqg (sigma =
+    rho there)."""
     inst = np.arange(first, first + B, dtype=np.uint64)
     out = np.zeros((B, 6))
     k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
     for j in range(3):
-        w0, w1, w2, w3 = philox4x32_10(inst, np.full(B, step), np.full(B, j), np.zeros(B), np.full(B, k0), np.full(B, k1))
+        w0, w1, w2, w3 = philox4x32_10(inst, np.full(B, step), np.full(B, j), np.full(B, int(word3)), np.full(B, k0), np.full(B, k1))
         uni = lambda a, b: ((a >> np.uint64(5)).astype(np.float64) * 67108864.0 + (b >> np.uint64(6)).astype(np.float64) + 1.0) * 2.0 ** -53
         u1, u2 = uni(w0, w1), uni(w2, w3)
         rad = np.sqrt(-2.0 * np.log(u1))

@@ -7,7 +7,7 @@ JSON line.
     python examples/run_tracking_ensemble.py [--data Data] [--members 65536] [--sigma 1e-3 1e-3 1e-2 1e-4 1e-3 1e-4]
                                              [--delta 0.3 0.3 0.5 0.05 0.1 0.05] [--seed 1] [--dt 1e-3]
                                              [--envelope FILE.npz] [--quantiles FILE.npz [--q 0.05 0.5 0.95]]
-                                             [--predict FILE.npz]
+                                             [--predict FILE.npz] [--rho r0 r1 r2 r3 r4 r5]
 
 --envelope FILE.npz: also reduce over the members at every sample on the device (the tube around the optimum) and save
 n (T,), min_dx / max_dx (6,T), min_du / max_du (2,T), mean_dx (6,T), cov_dx (6,6,T), raw (T,44); the JSON line then
@@ -20,6 +20,10 @@ line then carries "quantiles": the file, q and the largest width of the tube (la
 tracking gains, from the population moments of the initial perturbation, --delta, and --sigma) and save mean_dx (6,T),
 cov_dx (6,6,T), mean_du (2,T), cov_du (2,2,T), raw (T,32): the tube the sampled one of --envelope is read against; the JSON
 line then carries "predict": the file and the largest predicted standard deviation per state.
+--rho r0 .. r5: no member feeds back its true state but a Kalman estimate from measurements of the deviation with noise of
+these standard deviations (batch.filter_gains about the optimum, prior spread --delta, --sigma; aoc_track_ensemble_lqg); the
+JSON line then carries "rho" and "rms_estimation_error", per channel the root of the mean over members and samples of the
+squared estimation error.  Not together with --envelope, --quantiles or --predict.
 """
 import argparse
 import json
@@ -43,21 +47,30 @@ def main():
     ap.add_argument("--envelope", default=None, metavar="FILE.npz", help="save the per-sample envelope over the members")
     ap.add_argument("--quantiles", default=None, metavar="FILE.npz", help="save per-sample quantile tubes over the members")
     ap.add_argument("--predict", default=None, metavar="FILE.npz", help="save the linear prediction of mean and covariance")
+    ap.add_argument("--rho", type=float, nargs=6, default=None, help="std of the measurement noise: a Kalman estimate in the loop")
     ap.add_argument("--q", type=float, nargs="+", default=[0.05, 0.5, 0.95], help="quantile levels of --quantiles")
     a = ap.parse_args()
+    if a.rho is not None and (a.envelope or a.quantiles or a.predict):
+        ap.error("--rho does not combine with --envelope, --quantiles or --predict")
     xx_opt = np.load(os.path.join(a.data, "xx_star.npy"))
     uu_opt = np.load(os.path.join(a.data, "uu_star.npy"))
     T = xx_opt.shape[1]
     Q, R, QT = problems.tracking_weights()                           # lqr_tracking.py:324-328
     bp = batch.BatchProblem(Q, R, QT, np.zeros((6, T)), np.zeros((2, T)), a.dt)
     delta = np.random.default_rng(a.seed).normal(size=(a.members, 6)) * np.asarray(a.delta)
-    r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, envelope=a.envelope is not None,
-                             quantiles=a.q if a.quantiles is not None else None, predict=a.predict is not None,
-                             mean0=np.zeros(6), Sigma0=np.diag(np.asarray(a.delta) ** 2))
+    if a.rho is not None:
+        L = batch.filter_gains(bp, xx_opt, uu_opt, np.diag(np.asarray(a.delta) ** 2), a.sigma, a.rho)[0]
+        r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, filter=L, rho=a.rho)
+    else:
+        r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, envelope=a.envelope is not None,
+                                 quantiles=a.q if a.quantiles is not None else None, predict=a.predict is not None,
+                                 mean0=np.zeros(6), Sigma0=np.diag(np.asarray(a.delta) ** 2))
     sm = r["summary"][0]
     tolist = lambda d: {k: np.asarray(v).tolist() for k, v in d.items()}
     line = dict(members=a.members, T=T, sigma=a.sigma, left_the_domain=sm["n_bad"],
                 max_dx=tolist(sm["max_dx"]), final_dx=tolist(sm["final_dx"]), cost=tolist(sm["cost"]))
+    if a.rho is not None:
+        line.update(rho=list(a.rho), rms_estimation_error=np.sqrt(r["sum_e2"].mean(axis=0) / T).tolist())
     if a.envelope is not None:
         env = r["envelope"][0]
         np.savez(a.envelope, **env)

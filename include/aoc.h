@@ -64,7 +64,9 @@ extern "C" {
  *      (still 5, an addition: aoc_track_ensemble_histogram, aoc_ensemble_histogram_scratch_bytes — no struct, argument list
  *      or size query of an existing entry changed)
  *      (still 5, an addition: aoc_track_covariance, aoc_track_covariance_scratch_bytes — no struct, argument list or size
- *      query of an existing entry changed) */
+ *      query of an existing entry changed)
+ *      (still 5, an addition: aoc_track_ensemble_lqg, aoc_track_ensemble_lqg_scratch_bytes — no struct, argument list or
+ *      size query of an existing entry changed) */
 #define AOC_ABI_VERSION 5
 
 #define AOC_TILE 64
@@ -632,6 +634,45 @@ size_t aoc_track_covariance_scratch_bytes(int32_t n_opt, int32_t T);
 int aoc_track_covariance(const aoc_problem *prob, int32_t n_opt, const double *nominal, const double *mean0,
                          const double *Sigma0, const aoc_mpc_noise *noise, double *pred, int32_t *status, void *scratch,
                          size_t scratch_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The same ensemble with NOISY MEASUREMENTS and a KALMAN ESTIMATE in the loop: no member feeds back its true state.  Member b
+ * of optimum k starts with e^-_0 = ehat0[k] and runs, for t = 0 .. T-1,
+ *     dx_t = x_t - x_opt_t                          y_t = dx_t + v_t
+ *     e^+_t = e^-_t + L_t (y_t - e^-_t)             e_t = dx_t - e^+_t
+ *     t <= T-2:   u_t = u_opt_t + K_t e^+_t         x_{t+1} = Dynamics.step(x_t, u_t) + d_t     (the plant of aoc_track_ensemble)
+ *                 e^-_{t+1} = F_t e^+_t + c_t       (F_t = A_t + B_t K_t and c_t as defined for aoc_track_covariance)
+ * — a Kalman filter linearised about the optimum: its gains L_t depend on the optimum only and are the caller's (e.g. the
+ * Riccati recursion L = P^-(P^- + V)^-1 on the host).  L_t (y_t - e^-_t) and F_t e^+_t are sums from +0.0 in index order, every
+ * product fused into its addition, added once to e^-_t resp. c_t; u_t is summed as in aoc_track_ensemble.  So with L = 0,
+ * ehat0 = NULL and an optimum that is a rollout (c = 0) the estimate stays exactly +0.0 and u = u_opt.
+ * Every argument shared with aoc_track_ensemble means what it means there and is checked as there.  The others:
+ * filter: DEVICE, fp64, [n_opt][T][36], L_t row-major; all T samples are used.  Not NULL.
+ * ehat0: DEVICE, [n_opt][6], or NULL = 0: the prior estimate of dx_0, shared by the members of an optimum.
+ * rho: HOST, 6 doubles, or NULL: the standard deviations of the measurement noise.  v_t[c] = rho[c] * z, z from the generator
+ *   of the disturbance with key = noise->seed and counter (noise->first + b, noise->step + t, c/2, 1) — the fourth word is 1
+ *   where the disturbance has 0, so the two streams never share a counter — again a function of (seed, global member index,
+ *   step) alone.  NULL or all zero: no draw is made and v = +0.0.  The seed lives in `noise`: rho without noise is AOC_EINVAL
+ *   (noise->sigma may be all zero); so is a negative or non-finite rho.
+ * Outputs: x_reg, u_reg, dist_out, stats[AOC_ENS_NSTAT] and status are those of aoc_track_ensemble on THIS loop's
+ *   trajectories.  xhat_reg (tiled C=6, may be NULL): x_opt_t + e^+_t.  meas_out (tiled C=6, may be NULL): v_t, every sample.
+ *   est_stats: [ntiles][AOC_LQG_NSTAT][64], not NULL: 0-5 max over t of |e_t[c]| (a NaN sticks), 6-11 the sum over t of
+ *   e_t[c]^2 in sample order.  The statistics do not depend on which of the trajectory outputs are written.
+ * scratch: DEVICE, caller-owned, 16-byte aligned, at least aoc_track_ensemble_lqg_scratch_bytes(n_opt, T) bytes (0 for a
+ *   geometry the call refuses); the layout is private.  Nothing is allocated.
+ * AOC_EINVAL with the reason, before anything touches a device: the refusals of aoc_track_ensemble (T < 3 among them);
+ * filter or est_stats NULL; the rho rules; scratch NULL, misaligned or too small.
+ * Two kernels on prob->stream: the first kernel of aoc_track_covariance (F_t, c_t of every optimum and sample, into
+ * scratch), then the ensemble kernel, whose wavefronts stage F_t, c_t and L_t through LDS beside the nominal.  No atomics, a
+ * fixed order of every sum: a member's bits depend on (its optimum, its initial state, seed, global member index) only.
+ * --------------------------------------------------------------------------------------------- */
+#define AOC_LQG_NSTAT 12
+size_t aoc_track_ensemble_lqg_scratch_bytes(int32_t n_opt, int32_t T);
+int aoc_track_ensemble_lqg(const aoc_problem *prob, int32_t n_opt, int32_t members_per_opt, const double *nominal,
+                           const double *filter, const double *x0_reg, const double *ehat0, const aoc_mpc_noise *noise,
+                           const double *rho, void *x_reg, double *u_reg, double *xhat_reg, double *dist_out,
+                           double *meas_out, double *stats, double *est_stats, int32_t *status, void *scratch,
+                           size_t scratch_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * float32 arithmetic (BASELINE.json configs[2]: "fp32 with tolerance sweep").

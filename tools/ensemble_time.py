@@ -2,7 +2,7 @@
 """Closed-loop tracking ensemble about ONE optimum: aoc_track_ensemble against the replicated path it replaces.
 
     python tools/ensemble_time.py [--members 65536 262144] [--T 1000] [--seconds 0.5] [--repeats 3] [--out FILE]
-                                  [--envelope] [--histogram]
+                                  [--envelope] [--histogram] [--predict] [--lqg]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/ensemble_time.py --trace --members N
     python tools/ensemble_time.py --kernel-times DIR                 (kernel times: a traced run of its own, then its summary)
 
@@ -35,6 +35,11 @@ and 1024 windows of the optimum (--T at most 800 leaves room for them; otherwise
              a stage loop of batched fp64 matmuls on the device (F P F^T + W, F m + c, K m, K P K^T)
 against B_stats and B_env of the same run (the cheapest Monte-Carlo answers), and the quantile route on the device: two
 passes B_env + H against one pass P_1 + H.
+--lqg adds the loop with noisy measurements and a Kalman estimate (aoc_track_ensemble_lqg, statistics only, both kernels;
+gains from batch.filter_gains, rho = 0.1 of the members' spread):
+  L_plain    no disturbance and no measurement noise drawn (against B_stats)
+  L_noise    the disturbance and the measurement noise drawn on the device (against B_noise)
+and reports L_noise / B_noise and L_plain / B_stats of the same run.
 The optimum is the g4 fixture's (T = 1000; --T cuts it), the members are seeded perturbations of its first sample.
 Profiler off: HIP events around at least --seconds of back-to-back launches per variant, after a warm-up of every variant;
 the variants take turns inside each of --repeats rounds, so that a drift of the machine hits all of them.  One JSON line:
@@ -59,7 +64,7 @@ DELTA_SCALE = np.array([0.3, 0.3, 0.5, 0.05, 0.1, 0.05])
 SIGMA = np.array([1e-3, 1e-3, 1e-2, 1e-4, 1e-3, 1e-4])
 
 
-def setup(B, T, g, envelope=False, histogram=False):
+def setup(B, T, g, envelope=False, histogram=False, lqg=False):
     """Device buffers and the launch closures for B members."""
     import torch
     from aircraftoptimalcontrol_amd import _lib, batch
@@ -97,6 +102,22 @@ def setup(B, T, g, envelope=False, histogram=False):
                                        _ptr(status)), "aoc_track_ensemble")
 
     runs = dict(A=run_A, B_stats=run_B, B_traj=lambda: run_B(traj=True), B_noise=lambda: run_B(noise=True))
+    if lqg:
+        rho = 0.1 * DELTA_SCALE
+        Lf = batch.filter_gains(bp, xo, uo, np.diag(DELTA_SCALE ** 2), SIGMA, rho)[0]
+        filt = torch.from_numpy(np.ascontiguousarray(Lf.reshape(36, T).T)[None]).to(dev)        # [1][T][36]
+        est_stats = torch.empty((nt, batch.LQG_NSTAT, TILE), dtype=torch.float64, device=dev)
+        nbytes = int(lib().aoc_track_ensemble_lqg_scratch_bytes(1, T))
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        rho_c = (C.c_double * 6)(*rho.tolist())
+
+        def run_L(noise=False):
+            check(lib().aoc_track_ensemble_lqg(C.byref(pB), 1, nt * TILE, _ptr(nominal), _ptr(filt), _ptr(x0t), None,
+                                               C.byref(nz) if noise else None, rho_c if noise else None, None, None, None, None,
+                                               None, _ptr(stats), _ptr(est_stats), _ptr(status), _ptr(scratch), nbytes),
+                  "aoc_track_ensemble_lqg")
+
+        runs.update(L_plain=run_L, L_noise=lambda: run_L(noise=True))
     if not envelope and not histogram:
         return runs
     # E: trajectories in fp64 + a torch reduction on the tiled arrays [tile][t][c][lane]
@@ -331,6 +352,7 @@ def main():
     ap.add_argument("--envelope", action="store_true", help="also time the per-sample envelope: E_traj + E_reduce against B_env")
     ap.add_argument("--histogram", action="store_true", help="also time the per-sample histogram: H against B_stats, B_env and Q")
     ap.add_argument("--predict", action="store_true", help="also time aoc_track_covariance for 1, 64 and 1024 optima")
+    ap.add_argument("--lqg", action="store_true", help="also time aoc_track_ensemble_lqg, statistics only, with and without draws")
     ap.add_argument("--hist-valu", type=int, default=0, help="vector instructions per stage of the histogram kernel (from the ISA)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -344,10 +366,10 @@ def main():
     for B in a.members:
         rec = dict(members=B)
         try:
-            runs = setup(B, a.T, g, a.envelope, a.histogram or a.predict)
+            runs = setup(B, a.T, g, a.envelope, a.histogram or a.predict, a.lqg)
             if a.predict:
                 if not a.histogram:       # the yardsticks of the prediction only, not the torch routes to the histogram
-                    runs = {k: f for k, f in runs.items() if k in ("A", "B_stats", "B_env", "H")}
+                    runs = {k: f for k, f in runs.items() if k in ("A", "B_stats", "B_env", "H", "L_plain", "L_noise")}
                 runs.update(setup_predict(a.T, g))
         except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
             rec["refused"] = "allocation refused: %s" % str(e).split("\n")[0]
@@ -379,6 +401,12 @@ def main():
                                       P1_over_C=round(med["P_1"] / med["B_stats"], 4),
                                       two_pass_ms=round(med["B_env"] + med["H"], 4), one_pass_ms=round(med["P_1"] + med["H"], 4),
                                       spread_rel={k: sp(k) for k in ("P_1", "P_64", "P_1024", "B_stats", "B_env", "H")})
+            if a.lqg:
+                sp = lambda k: round((max(ms[k]) - min(ms[k])) / med[k], 4)
+                rec["lqg"] = dict(L_plain_ms=med["L_plain"], L_noise_ms=med["L_noise"], B_stats_ms=med["B_stats"],
+                                  B_noise_ms=med["B_noise"], L_noise_over_B_noise=round(med["L_noise"] / med["B_noise"], 4),
+                                  L_plain_over_B_stats=round(med["L_plain"] / med["B_stats"], 4),
+                                  spread_rel={k: sp(k) for k in ("L_plain", "L_noise", "B_stats", "B_noise")})
             if a.envelope:
                 E = med["E_traj"] + med["E_reduce"]
                 rec["envelope"] = dict(E_ms=round(E, 4), B_env_over_E=round(med["B_env"] / E, 4),
