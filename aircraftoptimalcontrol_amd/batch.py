@@ -987,6 +987,7 @@ HIST_NCH = _lib.AOC_HIST_NCH       # channels of aoc_track_ensemble_histogram: d
 HIST_NBIN = _lib.AOC_HIST_NBIN     # bins per (optimum, sample, channel)
 COV_NREC = _lib.AOC_COV_NREC       # doubles per (optimum, sample) record of aoc_track_covariance
 LQG_NSTAT = _lib.AOC_LQG_NSTAT     # estimation-error statistics per member of aoc_track_ensemble_lqg
+FILT_NREC = _lib.AOC_FILT_NREC     # doubles per (optimum, sample) covariance record of aoc_filter_gains
 # the record (include/aoc.h): n | min dx | max dx | min du | max du | sum dx | sum dx_i dx_j (upper triangle, row by row)
 _ENV_MIN = np.r_[1:7, 13:15]
 _ENV_MAX = np.r_[7:13, 15:17]
@@ -1289,6 +1290,67 @@ def filter_gains(problem, xx_opt, uu_opt, Sigma0, sigma, rho, jac=None):
     return L, Pm, Pp
 
 
+def _measured_mask(measured):
+    """a sequence of channel indices, or None = all six -> the 6-bit mask of aoc_filter_gains"""
+    if measured is None:
+        return 63
+    mask = 0
+    for c in measured:
+        if int(c) != c or not 0 <= int(c) < 6:
+            raise ValueError("measured must be channel indices 0 .. 5 (or None = all), got %r" % (measured,))
+        mask |= 1 << int(c)
+    return mask
+
+
+def _filter_gains_device(problem, nominal, n_opt, Sigma0, sigma, rho, mask, want_cov):
+    """aoc_filter_gains on a device `nominal` (n_opt,T,20), on the current stream -> device tensors filter (n_opt,T,36),
+    cov (n_opt,T,42) or None, status (n_opt,).  The rho rules are the call's own: a refusal is an AocError with its reason."""
+    torch = _torch()
+    dev, T = problem.device, problem.T
+    S0 = _dev_f64(_sym_upper(Sigma0, n_opt), dev)
+    nz = None
+    if sigma is not None:
+        nz = _lib.MpcNoise(0, 0, 0, (C.c_double * 6)(*np.asarray(sigma, dtype=np.float64).reshape(6).tolist()))
+    rho_c = (C.c_double * 6)(*np.asarray(rho, dtype=np.float64).reshape(6).tolist())
+    filt = torch.empty((n_opt, T, 36), dtype=torch.float64, device=dev)
+    cov = torch.empty((n_opt, T, FILT_NREC), dtype=torch.float64, device=dev) if want_cov else None
+    status = torch.zeros(n_opt, dtype=torch.int32, device=dev)
+    nbytes = int(lib().aoc_filter_gains_scratch_bytes(n_opt, T))
+    scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    p = problem.c_problem(n_opt)
+    check(lib().aoc_filter_gains(C.byref(p), n_opt, _ptr(nominal), _ptr(S0), C.byref(nz) if nz is not None else None, rho_c,
+                                 mask, _ptr(filt), _ptr(cov), _ptr(status), _ptr(scratch), nbytes), "aoc_filter_gains")
+    return filt, cov, status
+
+
+def filter_gains_device(problem, xx_opt, uu_opt, Sigma0, sigma, rho, measured=None, to_host=True):
+    """filter_gains for n_opt optima in ONE call, on the device (aoc_filter_gains), and for a filter that measures only some
+    of the six channels: y = H dx + v, H the rows `measured` of the identity (a sequence of channel indices; None = all), V =
+    diag(rho^2) of those channels — the rho of an unmeasured channel is not read.  The measurement update takes one scalar
+    measurement at a time (include/aoc.h), so its values differ from filter_gains' Joseph form in the last digits.
+    xx_opt (6,T) or (n_opt,6,T), uu_opt likewise; Sigma0 (6,6) or (n_opt,6,6), symmetric (checked here); sigma (6,) or None.
+    Returns L (n_opt,6,6,T), P_prior (n_opt,6,6,T), P_post (n_opt,6,6,T), status (n_opt,) — numpy, or device tensors with
+    to_host=False.  An unmeasured column of L is exactly +0.0."""
+    torch = _torch()
+    xo, uo = np.asarray(xx_opt, dtype=np.float64), np.asarray(uu_opt, dtype=np.float64)
+    if xo.ndim == 2:
+        xo, uo = xo[None], uo[None]
+    n_opt, T = xo.shape[0], problem.T
+    if xo.shape != (n_opt, 6, T) or uo.shape != (n_opt, 2, T):
+        raise ValueError("xx_opt must be (6,T) or (n_opt,6,T) with T = %d, uu_opt likewise" % T)
+    mask = _measured_mask(measured)
+    nominal = torch.from_numpy(ensemble_nominal(xo, uo, np.zeros((n_opt, 2, 6, T)))).to(problem.device)
+    filt, cov, status = _filter_gains_device(problem, nominal, n_opt, Sigma0, sigma, rho, mask, True)
+    iu = torch.as_tensor(np.concatenate([_ENV_TRI[0] * 6 + _ENV_TRI[1], _ENV_TRI[1] * 6 + _ENV_TRI[0]]), device=problem.device)
+    full = []
+    for half in (cov[:, :, :21], cov[:, :, 21:]):
+        P = torch.empty((n_opt, T, 36), dtype=torch.float64, device=problem.device)
+        P[:, :, iu] = torch.cat([half, half], dim=2)
+        full.append(P.reshape(n_opt, T, 6, 6).permute(0, 2, 3, 1).contiguous())
+    out = (filt.reshape(n_opt, T, 6, 6).permute(0, 2, 3, 1).contiguous(), full[0], full[1], status)
+    return tuple(t.cpu().numpy() for t in out) if to_host else out
+
+
 def _ens_summary(torch, v):
     """mean / max / quantiles over the members (rows) of one optimum, reduced on the device"""
     q = torch.quantile(v, torch.tensor(ENS_QUANTILES, dtype=v.dtype, device=v.device), dim=0)
@@ -1300,7 +1362,7 @@ def _ens_summary(torch, v):
 def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, sigma=None, seed=20260405, first=0,
                    step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True, envelope=False,
                    quantiles=None, bins=None, predict=False, mean0=None, Sigma0=None, predict_k=6.0, rho=None, filter=None,
-                   ehat0=None):
+                   ehat0=None, measured=None):
     """Closed-loop tracking ensemble about shared optima (aoc_track_ensemble): the loop of lqr_tracking.py:279-281 for B
     members, u_t = u_opt_t + K_t (x_t - x_opt_t), x_{t+1} = step(x_t, u_t) + d_t, reduced to per-member statistics on
     the device; the optimum and its gains are stored once per optimum, not once per member.
@@ -1342,8 +1404,22 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     (n_opt,6): the prior estimate of dx_0 of each optimum's members, None = 0.  Every output above is then that of this
     loop; added: est_stats (B,12), max_e (B,6) = max_t |e_t| and sum_e2 (B,6) = sum_t e_t^2 of the estimation error e_t =
     dx_t - e^+_t, and with trajectories=True xhat (B,6,T) = x_opt_t + e^+_t and meas (B,6,T) = v_t.  rho= or ehat0= without
-    filter=, and filter= together with envelope=, quantiles= or predict=, raise ValueError."""
+    filter=, and filter= together with envelope=, quantiles= or predict=, raise ValueError.
+    filter="device" (aoc_filter_gains, then aoc_track_ensemble_lqg on the same stream): the gains of all n_opt optima are
+    computed on the device by ONE call and handed over as they lie — nothing of L visits the host.  The filter is built on
+    Sigma0 (6,6) / (n_opt,6,6), the covariance of the prior estimate's error (required: ValueError without it), the call's
+    sigma and rho (required), and measures the channels `measured` (a sequence of indices; None = all; filter_gains_device).
+    The members' measurement noise is still drawn in all six channels with rho.  Adds `filter_status` (n_opt,)."""
     lqg = filter is not None
+    device_gains = isinstance(filter, str)
+    if device_gains:
+        if filter != "device":
+            raise ValueError('filter=%r: the only name is "device"' % (filter,))
+        if Sigma0 is None or rho is None:
+            raise ValueError('filter="device" needs Sigma0= (the covariance of the prior estimate\'s error) and rho=')
+        mask = _measured_mask(measured)
+    elif measured is not None:
+        raise ValueError('measured= goes with filter="device"')
     if not lqg and (rho is not None or ehat0 is not None):
         raise ValueError("rho= and ehat0= go with filter= (the gains of the estimator, e.g. from filter_gains)")
     if lqg and (envelope or quantiles is not None or predict or bins is not None):
@@ -1438,11 +1514,14 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
               "aoc_track_ensemble_histogram")
         del scratch
     if lqg:
-        Lf = np.asarray(filter, dtype=np.float64)
-        Lf = Lf[None] if Lf.ndim == 3 else Lf
-        if Lf.shape != (n_opt, 6, 6, T):
-            raise ValueError("filter must be (6,6,T) or (n_opt,6,6,T) = %s, got %s" % ((n_opt, 6, 6, T), Lf.shape))
-        filt_d = torch.from_numpy(np.ascontiguousarray(Lf.reshape(n_opt, 36, T).transpose(0, 2, 1))).to(dev)   # [opt][t][36]
+        if device_gains:
+            filt_d, _, filt_status = _filter_gains_device(problem, nominal, n_opt, Sigma0, sigma, rho, mask, False)
+        else:
+            Lf = np.asarray(filter, dtype=np.float64)
+            Lf = Lf[None] if Lf.ndim == 3 else Lf
+            if Lf.shape != (n_opt, 6, 6, T):
+                raise ValueError("filter must be (6,6,T) or (n_opt,6,6,T) = %s, got %s" % ((n_opt, 6, 6, T), Lf.shape))
+            filt_d = torch.from_numpy(np.ascontiguousarray(Lf.reshape(n_opt, 36, T).transpose(0, 2, 1))).to(dev)   # [opt][t][36]
         e0_d = None
         if ehat0 is not None:
             e0 = np.asarray(ehat0, dtype=np.float64)
@@ -1483,6 +1562,8 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     if lqg:
         es = unpack_vec(est_stats, B).cpu().numpy()
         out.update(est_stats=es, max_e=es[:, 0:6], sum_e2=es[:, 6:12])
+        if device_gains:
+            out["filter_status"] = filt_status.cpu().numpy()
     if envelope:
         out["envelope"] = [_envelope_dict(r) for r in env.cpu().numpy()]
     if predict:

@@ -7,7 +7,7 @@
 // No MFMA (the blocks are 6x6/6x2); the per-lane state (P: 21, p: 6, lambda: 6 doubles, ...) lives in VGPRs.
 // The kernels themselves are in aoc_passes.inc (which includes passes/*.inc, one file per pass: layout, unit, cost_rollout,
 // backward, forward, tracking, hcut, ltv_lqr, linesearch, mpc; then the launch functions api.inc and the solve loop
-// solve.inc, and ensemble.inc, covariance.inc and lqg.inc with their own launch functions) + aoc_device.h, compiled twice: fp64 (aoc64, the parity path) and float32 (aoc32, BASELINE config 3); this file
+// solve.inc, and ensemble.inc, covariance.inc, lqg.inc and filter.inc with their own launch functions) + aoc_device.h, compiled twice: fp64 (aoc64, the parity path) and float32 (aoc32, BASELINE config 3); this file
 // holds what is common and the C-ABI.
 #include <hip/hip_runtime.h>
 
@@ -564,6 +564,15 @@ int aoc_track_ensemble_lqg(const aoc_problem* p, int32_t n_opt, int32_t members_
     static_assert(aoc64::EST_NSTAT == AOC_LQG_NSTAT, "estimation statistics of the kernel and of the header");
     return aoc64::api_track_ensemble_lqg(p, n_opt, members_per_opt, nominal, filter, x0_reg, ehat0, noise, rho, x_reg, u_reg,
                                          xhat_reg, dist_out, meas_out, stats, est_stats, status, scratch, scratch_bytes);
+}
+
+size_t aoc_filter_gains_scratch_bytes(int32_t n_opt, int32_t T) { return aoc64::filter_gains_scratch_bytes(n_opt, T); }
+
+int aoc_filter_gains(const aoc_problem* p, int32_t n_opt, const double* nominal, const double* Sigma0,
+                     const aoc_mpc_noise* noise, const double* rho, int32_t measured, double* filter, double* cov,
+                     int32_t* status, void* scratch, size_t scratch_bytes) {
+    static_assert(aoc64::FILT_NREC == AOC_FILT_NREC, "covariance record of the kernel and of the header");
+    return aoc64::api_filter_gains(p, n_opt, nominal, Sigma0, noise, rho, measured, filter, cov, status, scratch, scratch_bytes);
 }
 
 // ---- float32 arithmetic (aoc32): every array, the reference curves and the workspace are float32 ------

@@ -23,5 +23,6 @@ namespace AOC_ARITH_NS {
 #include "passes/ensemble.inc"   // kernel and launch function in one file (the latter uses make_const of api.inc)
 #include "passes/covariance.inc" // likewise (the nominal's record is that of ensemble.inc)
 #include "passes/lqg.inc"        // launch function only: k_cov_stage of covariance.inc, then the EST instance of ensemble.inc
+#include "passes/filter.inc"     // the filter's gains: k_cov_stage without B K, then a chain kernel of its own
 
 }  // namespace AOC_ARITH_NS

@@ -46,7 +46,9 @@ static_assert(COV_REC % 2 == 0 && COV_O_K % 2 == 0, "rows of F and K start on 16
 
 struct CovW { double w[6]; };   // sigma^2
 
-template <typename = void>
+// BK = false (filter.inc): the record holds A_t instead of F_t — a filter knows its input — and the gains, which it does not
+// read, do not count as entries of the optimum's record.
+template <bool BK = true>
 __global__ __launch_bounds__(COV_THREADS) void k_cov_stage(KConst k, int n_opt, const real* __restrict__ nominal,
                                                            real* __restrict__ rec) {
     const int T = k.T;
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(COV_THREADS) void k_cov_stage(KConst k, int n_opt, 
 #pragma unroll
     for (int j = 0; j < ENS_REC; j++) {
         v[j] = nm[j];
-        fin = fin && __builtin_isfinite(v[j]);
+        if (BK || j < 8) fin = fin && __builtin_isfinite(v[j]);
     }
 #pragma unroll
     for (int c = 0; c < 6; c++) xnext[c] = t < T - 1 ? nm[ENS_REC + c] : v[c];
@@ -76,11 +78,13 @@ __global__ __launch_bounds__(COV_THREADS) void k_cov_stage(KConst k, int n_opt, 
     F[0 * 6 + 2] = l.a02; F[0 * 6 + 5] = l.a05; F[1 * 6 + 2] = l.a12; F[1 * 6 + 5] = l.a15;
     F[2 * 6 + 2] = l.a22; F[2 * 6 + 3] = l.a23; F[2 * 6 + 5] = l.a25;
     F[5 * 6 + 2] = l.a52; F[5 * 6 + 3] = l.a53; F[5 * 6 + 5] = l.a55;
+    if constexpr (BK) {
 #pragma unroll
-    for (int j = 0; j < 6; j++) {   // F = A + B K: B has the entries (2,0), (5,0) and (4,1)
-        F[2 * 6 + j] = fma_r(l.b20, v[8 + j], F[2 * 6 + j]);
-        F[5 * 6 + j] = fma_r(l.b50, v[8 + j], F[5 * 6 + j]);
-        F[4 * 6 + j] = fma_r(k.b41, v[14 + j], F[4 * 6 + j]);
+        for (int j = 0; j < 6; j++) {   // F = A + B K: B has the entries (2,0), (5,0) and (4,1)
+            F[2 * 6 + j] = fma_r(l.b20, v[8 + j], F[2 * 6 + j]);
+            F[5 * 6 + j] = fma_r(l.b50, v[8 + j], F[5 * 6 + j]);
+            F[4 * 6 + j] = fma_r(k.b41, v[14 + j], F[4 * 6 + j]);
+        }
     }
     real2v* __restrict__ out = (real2v*)(rec + idx * COV_REC);
 #pragma unroll
@@ -90,6 +94,34 @@ __global__ __launch_bounds__(COV_THREADS) void k_cov_stage(KConst k, int n_opt, 
 #pragma unroll
     for (int e = 0; e < 6; e++) out[COV_O_K / 2 + e] = real2v{v[8 + 2 * e], v[9 + 2 * e]};
     out[COV_O_FLAG / 2] = real2v{(real)flags, R(0.0)};
+}
+
+// What the chain kernels (k_cov_chain here, k_filter_chain of filter.inc) share.  The stream of k_cov_stage's records: block b
+// = the records of the samples b*COV_BLK .., COV_PF doubles per lane, clamped onto the optimum's last double; fetched into
+// registers a block ahead, then stashed into one half of an LDS double buffer.
+__device__ __forceinline__ void cov_fetch(const real* __restrict__ rc, size_t nrec, int b, int L, real pf[COV_PF]) {
+#pragma unroll
+    for (int i = 0; i < COV_PF; i++) {
+        const size_t e = (size_t)b * COV_BLK * COV_REC + i * TILE + L;
+        pf[i] = rc[e < nrec ? e : nrec - 1];
+    }
+}
+__device__ __forceinline__ void cov_stash(real* __restrict__ half, int L, const real pf[COV_PF]) {
+#pragma unroll
+    for (int i = 0; i < COV_PF; i++) half[i * TILE + L] = pf[i];
+    __syncthreads();   // one wavefront: orders the LDS writes before the reads
+}
+// a 6-term product from +0.0, two chains of three fused multiply-adds, plus `add`
+__device__ __forceinline__ real dot6(const real a[6], const real b[6], real add) {
+    const real s0 = fma_r(a[2], b[2], fma_r(a[1], b[1], fma_r(a[0], b[0], R(0.0))));
+    const real s1 = fma_r(a[5], b[5], fma_r(a[4], b[4], fma_r(a[3], b[3], R(0.0))));
+    return (s0 + s1) + add;
+}
+// six consecutive values, 16-byte aligned: three ds_read_b128
+__device__ __forceinline__ void row6(const real* __restrict__ p, real out[6]) {
+    const real2v* __restrict__ q = (const real2v*)p;
+#pragma unroll
+    for (int e = 0; e < 3; e++) { const real2v v2 = q[e]; out[2 * e] = v2.x; out[2 * e + 1] = v2.y; }
 }
 
 // LDS of k_cov_chain beside the stream's double buffer: st[2][48] the state (P full [36], m [6]) of even / odd samples,
@@ -134,28 +166,8 @@ __global__ __launch_bounds__(TILE) void k_cov_chain(int T, const real* __restric
     } else if (L < 32) src = COV_O + (L - 27);
 
     real pf[COV_PF];
-    auto fetch = [&](int b) {   // block b = the records of the samples b*COV_BLK .., clamped onto the optimum's last double
-#pragma unroll
-        for (int i = 0; i < COV_PF; i++) {
-            const size_t e = (size_t)b * COV_BLK * COV_REC + i * TILE + L;
-            pf[i] = rc[e < nrec ? e : nrec - 1];
-        }
-    };
-    auto stash = [&](int b) {
-#pragma unroll
-        for (int i = 0; i < COV_PF; i++) sh[b & 1][i * TILE + L] = pf[i];
-        __syncthreads();   // one wavefront: orders the LDS writes before the reads
-    };
-    auto dot6 = [](const real a[6], const real b[6], real add) {
-        const real s0 = __builtin_fma(a[2], b[2], __builtin_fma(a[1], b[1], __builtin_fma(a[0], b[0], R(0.0))));
-        const real s1 = __builtin_fma(a[5], b[5], __builtin_fma(a[4], b[4], __builtin_fma(a[3], b[3], R(0.0))));
-        return (s0 + s1) + add;
-    };
-    auto row6 = [](const real* __restrict__ p, real out[6]) {   // 16-byte aligned: three ds_read_b128
-        const real2v* __restrict__ q = (const real2v*)p;
-#pragma unroll
-        for (int e = 0; e < 3; e++) { const real2v v2 = q[e]; out[2 * e] = v2.x; out[2 * e + 1] = v2.y; }
-    };
+    auto fetch = [&](int b) { cov_fetch(rc, nrec, b, L, pf); };
+    auto stash = [&](int b) { cov_stash(sh[b & 1], L, pf); };
     // record t - 1 (state of parity (t - 1) & 1, the input moments as they lie) goes out
     auto emit = [&](int t_out, bool inputs) {
         if (L < COV_NREC) {

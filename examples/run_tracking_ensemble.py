@@ -7,7 +7,7 @@ JSON line.
     python examples/run_tracking_ensemble.py [--data Data] [--members 65536] [--sigma 1e-3 1e-3 1e-2 1e-4 1e-3 1e-4]
                                              [--delta 0.3 0.3 0.5 0.05 0.1 0.05] [--seed 1] [--dt 1e-3]
                                              [--envelope FILE.npz] [--quantiles FILE.npz [--q 0.05 0.5 0.95]]
-                                             [--predict FILE.npz] [--rho r0 r1 r2 r3 r4 r5]
+                                             [--predict FILE.npz] [--rho r0 r1 r2 r3 r4 r5 [--device-gains] [--measured c ...]]
 
 --envelope FILE.npz: also reduce over the members at every sample on the device (the tube around the optimum) and save
 n (T,), min_dx / max_dx (6,T), min_du / max_du (2,T), mean_dx (6,T), cov_dx (6,6,T), raw (T,44); the JSON line then
@@ -24,6 +24,9 @@ line then carries "predict": the file and the largest predicted standard deviati
 these standard deviations (batch.filter_gains about the optimum, prior spread --delta, --sigma; aoc_track_ensemble_lqg); the
 JSON line then carries "rho" and "rms_estimation_error", per channel the root of the mean over members and samples of the
 squared estimation error.  Not together with --envelope, --quantiles or --predict.
+--device-gains (takes effect only with --rho): the filter's gains are computed on the device (aoc_filter_gains) and handed to
+the ensemble as they lie, batch.track_ensemble(filter="device"); --measured c ...: the filter then measures these channels
+only (default: all six).  The JSON line then also carries "device_gains": true and "measured".
 """
 import argparse
 import json
@@ -48,6 +51,8 @@ def main():
     ap.add_argument("--quantiles", default=None, metavar="FILE.npz", help="save per-sample quantile tubes over the members")
     ap.add_argument("--predict", default=None, metavar="FILE.npz", help="save the linear prediction of mean and covariance")
     ap.add_argument("--rho", type=float, nargs=6, default=None, help="std of the measurement noise: a Kalman estimate in the loop")
+    ap.add_argument("--device-gains", action="store_true", help="with --rho: the filter's gains from aoc_filter_gains")
+    ap.add_argument("--measured", type=int, nargs="+", default=None, help="with --device-gains: the channels the filter measures")
     ap.add_argument("--q", type=float, nargs="+", default=[0.05, 0.5, 0.95], help="quantile levels of --quantiles")
     a = ap.parse_args()
     if a.rho is not None and (a.envelope or a.quantiles or a.predict):
@@ -58,7 +63,11 @@ def main():
     Q, R, QT = problems.tracking_weights()                           # lqr_tracking.py:324-328
     bp = batch.BatchProblem(Q, R, QT, np.zeros((6, T)), np.zeros((2, T)), a.dt)
     delta = np.random.default_rng(a.seed).normal(size=(a.members, 6)) * np.asarray(a.delta)
-    if a.rho is not None:
+    device_gains = a.rho is not None and a.device_gains
+    if device_gains:
+        r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, filter="device", rho=a.rho,
+                                 Sigma0=np.diag(np.asarray(a.delta) ** 2), measured=a.measured)
+    elif a.rho is not None:
         L = batch.filter_gains(bp, xx_opt, uu_opt, np.diag(np.asarray(a.delta) ** 2), a.sigma, a.rho)[0]
         r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, filter=L, rho=a.rho)
     else:
@@ -71,6 +80,8 @@ def main():
                 max_dx=tolist(sm["max_dx"]), final_dx=tolist(sm["final_dx"]), cost=tolist(sm["cost"]))
     if a.rho is not None:
         line.update(rho=list(a.rho), rms_estimation_error=np.sqrt(r["sum_e2"].mean(axis=0) / T).tolist())
+    if device_gains:
+        line.update(device_gains=True, measured=sorted(set(a.measured)) if a.measured is not None else list(range(6)))
     if a.envelope is not None:
         env = r["envelope"][0]
         np.savez(a.envelope, **env)

@@ -66,7 +66,9 @@ extern "C" {
  *      (still 5, an addition: aoc_track_covariance, aoc_track_covariance_scratch_bytes — no struct, argument list or size
  *      query of an existing entry changed)
  *      (still 5, an addition: aoc_track_ensemble_lqg, aoc_track_ensemble_lqg_scratch_bytes — no struct, argument list or
- *      size query of an existing entry changed) */
+ *      size query of an existing entry changed)
+ *      (still 5, an addition: aoc_filter_gains, aoc_filter_gains_scratch_bytes — no struct, argument list or size query of
+ *      an existing entry changed) */
 #define AOC_ABI_VERSION 5
 
 #define AOC_TILE 64
@@ -673,6 +675,46 @@ int aoc_track_ensemble_lqg(const aoc_problem *prob, int32_t n_opt, int32_t membe
                            const double *rho, void *x_reg, double *u_reg, double *xhat_reg, double *dist_out,
                            double *meas_out, double *stats, double *est_stats, int32_t *status, void *scratch,
                            size_t scratch_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The GAINS of that Kalman filter, for every optimum at once: the filter Riccati recursion about the optimum, for the
+ * measurement y = H dx + v with H a selection of the six channels (bit c of `measured`: channel c is measured) and
+ * V = diag(rho^2).  With v_c = rho[c]^2, W = diag(sigma^2), P^-_0 = Sigma0 and A_t the Jacobian of Dynamics.step at
+ * (x_opt_t, u_opt_t) — A, not F = A + B K: the filter knows its input — every sample t = 0 .. T-1 takes one scalar measurement
+ * at a time: Q = P^-_t, then for c = 0 .. 5 in this order, where channel c is measured, with s = 1 / (Q_cc + v_c),
+ *     row and column c:    Q_ic <- Q_ic (v_c s)             (multiplicative: nothing is subtracted)
+ *     every other entry:   Q_ij <- Q_ij - (Q_ic Q_cj) s
+ * and after the sixth channel
+ *     P^+_t = Q,     L_t[:, c] = P^+_t[:, c] / v_c  (measured c),     L_t[:, c] = +0.0  (unmeasured c),
+ *     t <= T-2:      P^-_{t+1} = A_t P^+_t A_t^T + W.
+ * This is L = P^- H^T (H P^- H^T + V)^-1 and P^+ = (I - L H) P^- without a matrix inverse or a pivot search; both halves of Q
+ * are one expression, so P is symmetric bit for bit.  With measured = 0 nothing is measured: L = 0, P^+ = P^-, and P^- has the
+ * bits of aoc_track_covariance's covariance on the same nominal with its gains set to zero.
+ * prob: model (with dt), T and stream are read; B, the weights, ref and the x_* flags are not.
+ * nominal: DEVICE, [n_opt][T][20], the array aoc_track_ensemble takes; its gains (entries 8-19) are ignored.
+ * Sigma0: DEVICE, [n_opt][21], the upper triangle row by row, or NULL = 0.
+ * noise: HOST, may be NULL (W = 0); only sigma[6] is read.
+ * rho: HOST, 6 doubles, not NULL; the rho of an unmeasured channel is not read.
+ * filter: DEVICE, fp64, [n_opt][T][36], L_t row-major: exactly the `filter` of aoc_track_ensemble_lqg.  Not NULL.
+ * cov: DEVICE, fp64, [n_opt][T][AOC_FILT_NREC], may be NULL: 0-20 the upper triangle of P^-_t row by row (the order of the
+ *   envelope's entries 23-43), 21-41 that of P^+_t.  filter has the same bits with and without it.
+ * status: DEVICE, [n_opt], may be NULL; OR-ed: AOC_ST_VNONPOS if !(V_opt_t > 0) at some t <= T-2, AOC_ST_NAN if an entry of the
+ *   optimum's states or inputs is not finite, AOC_ST_SINGULAR if a pivot Q_cc + v_c was not > 0 (a Sigma0 that is not positive
+ *   semidefinite).  Such an optimum yields whatever the arithmetic gives and disturbs no other.
+ * scratch: DEVICE, caller-owned, 16-byte aligned, at least aoc_filter_gains_scratch_bytes(n_opt, T) bytes (0 for a geometry
+ *   the call refuses); the layout is private.  Nothing is allocated.
+ * AOC_EINVAL with the reason, before anything touches a device: prob, nominal, filter or rho NULL; n_opt < 1; T < 3; measured
+ * outside 0 .. 63; a measured channel whose rho is not finite or not > 0; a negative or non-finite sigma; scratch NULL,
+ * misaligned or too small.
+ * Two kernels on prob->stream: the first kernel of aoc_track_covariance without its B K term (A_t of every optimum and
+ * sample, into scratch), then one wavefront per optimum for the recursion, whose lanes own the entries of Q.  No atomics, a
+ * fixed order: the same bits every run, and an optimum's records do not depend on n_opt or on its position in the call.
+ * --------------------------------------------------------------------------------------------- */
+#define AOC_FILT_NREC 42
+size_t aoc_filter_gains_scratch_bytes(int32_t n_opt, int32_t T);
+int aoc_filter_gains(const aoc_problem *prob, int32_t n_opt, const double *nominal, const double *Sigma0,
+                     const aoc_mpc_noise *noise, const double *rho, int32_t measured, double *filter, double *cov,
+                     int32_t *status, void *scratch, size_t scratch_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * float32 arithmetic (BASELINE.json configs[2]: "fp32 with tolerance sweep").

@@ -2,7 +2,7 @@
 """Closed-loop tracking ensemble about ONE optimum: aoc_track_ensemble against the replicated path it replaces.
 
     python tools/ensemble_time.py [--members 65536 262144] [--T 1000] [--seconds 0.5] [--repeats 3] [--out FILE]
-                                  [--envelope] [--histogram] [--predict] [--lqg]
+                                  [--envelope] [--histogram] [--predict] [--lqg] [--filter]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/ensemble_time.py --trace --members N
     python tools/ensemble_time.py --kernel-times DIR                 (kernel times: a traced run of its own, then its summary)
 
@@ -40,6 +40,12 @@ gains from batch.filter_gains, rho = 0.1 of the members' spread):
   L_plain    no disturbance and no measurement noise drawn (against B_stats)
   L_noise    the disturbance and the measurement noise drawn on the device (against B_noise)
 and reports L_noise / B_noise and L_plain / B_stats of the same run.
+--filter adds the filter Riccati recursion on the device (aoc_filter_gains, both kernels, gains only: cov = NULL), for n_opt =
+1, 64 and 1024 windows of the optimum as --predict takes them, prior diag(DELTA_SCALE^2), rho = 0.1 of it, all six channels:
+  G_n        aoc_filter_gains for n optima
+  P_n        aoc_track_covariance for n optima in the same run: the same chain without the downdates
+and reports G_n / P_n, and the host recursion batch.filter_gains for ONE optimum with the Jacobians already in hand (wall
+clock, the median of three).
 The optimum is the g4 fixture's (T = 1000; --T cuts it), the members are seeded perturbations of its first sample.
 Profiler off: HIP events around at least --seconds of back-to-back launches per variant, after a warm-up of every variant;
 the variants take turns inside each of --repeats rounds, so that a drift of the machine hits all of them.  One JSON line:
@@ -234,7 +240,52 @@ def setup(B, T, g, envelope=False, histogram=False, lqg=False):
     return runs
 
 
-def setup_predict(T, g, sizes=(1, 64, 1024)):
+def setup_filter(T, g, sizes=(1, 64, 1024)):
+    """Launch closures of aoc_filter_gains for each n_opt in `sizes`, and the host recursion's time for one optimum [ms]."""
+    import time
+    import torch
+    from aircraftoptimalcontrol_amd import _lib, batch
+    from aircraftoptimalcontrol_amd.batch import _ptr, check, lib
+    dev = torch.device("cuda:0")
+    Tg = g["xx_opt"].shape[1]
+    bp = batch.BatchProblem(g["QQt"], g["RRt"], g["QQT"], np.zeros((6, T)), np.zeros((2, T)), float(g["dt"]), device=dev)
+    nz = _lib.MpcNoise(20261016, 0, 0, (C.c_double * 6)(*SIGMA.tolist()))
+    rho = 0.1 * DELTA_SCALE
+    rho_c = (C.c_double * 6)(*rho.tolist())
+    S0 = torch.from_numpy(np.diag(DELTA_SCALE ** 2)[np.triu_indices(6)]).to(dev)
+    runs, filts = {}, {}
+    for n in sizes:
+        off = [(k % max(1, Tg - T + 1)) for k in range(n)]
+        xo = np.stack([g["xx_opt"][:, o:o + T] for o in off])
+        uo = np.stack([g["uu_opt"][:, o:o + T] for o in off])
+        nominal = torch.from_numpy(batch.ensemble_nominal(xo, uo, np.zeros((n, 2, 6, T)))).to(dev)
+        Sig = S0.repeat(n, 1).contiguous()
+        filt = torch.empty((n, T, 36), dtype=torch.float64, device=dev)
+        nbytes = int(lib().aoc_filter_gains_scratch_bytes(n, T))
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        p = bp.c_problem(n)
+
+        def run_G(p=p, n=n, nominal=nominal, Sig=Sig, filt=filt, scratch=scratch, nbytes=nbytes):
+            check(lib().aoc_filter_gains(C.byref(p), n, _ptr(nominal), _ptr(Sig), C.byref(nz), rho_c, 63, _ptr(filt), None, None,
+                                         _ptr(scratch), nbytes), "aoc_filter_gains")
+
+        runs["G_%d" % n], filts[n] = run_G, filt
+    xo, uo = g["xx_opt"][:, :T], g["uu_opt"][:, :T]
+    fx = batch.step_batch(bp.model, xo[:, :T - 1].T, uo[:, :T - 1].T, device=dev)[1]
+    A = fx.transpose(0, 2, 1)
+    host = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        Lh = batch.filter_gains(bp, xo, uo, np.diag(DELTA_SCALE ** 2), SIGMA, rho, jac=(A, None))[0]
+        host.append((time.perf_counter() - t0) * 1e3)
+    n0 = sizes[0]                                                                        # window 0: the two agree before either is timed
+    runs["G_%d" % n0](); torch.cuda.synchronize()
+    got = filts[n0][0].cpu().numpy().reshape(T, 6, 6).transpose(1, 2, 0)
+    assert np.abs(got - Lh).max() <= 1e-9 * np.abs(Lh).max(), "aoc_filter_gains and filter_gains disagree"
+    return runs, float(np.median(host))
+
+
+def setup_predict(T, g, sizes=(1, 64, 1024), torch_route=True):
     """Launch closures of the prediction for each n_opt in `sizes`, and of the torch route to the same records."""
     import torch
     from aircraftoptimalcontrol_amd import _lib, batch
@@ -297,10 +348,13 @@ def setup_predict(T, g, sizes=(1, 64, 1024)):
                 P = torch.matmul(torch.matmul(F[:, t], P), F[:, t].transpose(1, 2)) + W
             return out
 
+        runs["P_%d" % n] = run_P
+        if not torch_route:
+            continue
         run_P(); want = run_TQ(); torch.cuda.synchronize()                                # the two routes agree before either is timed
         scale = want.abs().amax(dim=(0, 1)).clamp(min=1e-300)
         assert bool((((pred - want).abs() / scale) <= 1e-9).all()), "P and TQ disagree"
-        runs["P_%d" % n], runs["TQ_%d" % n] = run_P, run_TQ
+        runs["TQ_%d" % n] = run_TQ
     return runs
 
 
@@ -334,7 +388,7 @@ def kernel_times(d):
     out = collections.OrderedDict()
     for name, t0, t1, grid in sorted(rows, key=lambda r: r[1]):
         name = name.split("(")[0].replace("void ", "").replace("aoc64::", "")
-        if name.startswith(("k_track_", "k_envelope_", "k_histogram_", "k_cov_")):
+        if name.startswith(("k_track_", "k_envelope_", "k_histogram_", "k_cov_", "k_filter_")):
             out.setdefault("%s grid=%s" % (name, grid), []).append(round((t1 - t0) / 1e6, 4))
     for k, v in out.items():
         print(json.dumps(dict(kernel=k, ms=v, median=float(np.median(v)), spread_rel=round((max(v) - min(v)) / float(np.median(v)), 4))))
@@ -353,6 +407,7 @@ def main():
     ap.add_argument("--histogram", action="store_true", help="also time the per-sample histogram: H against B_stats, B_env and Q")
     ap.add_argument("--predict", action="store_true", help="also time aoc_track_covariance for 1, 64 and 1024 optima")
     ap.add_argument("--lqg", action="store_true", help="also time aoc_track_ensemble_lqg, statistics only, with and without draws")
+    ap.add_argument("--filter", action="store_true", help="also time aoc_filter_gains for 1, 64 and 1024 optima")
     ap.add_argument("--hist-valu", type=int, default=0, help="vector instructions per stage of the histogram kernel (from the ISA)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -369,8 +424,13 @@ def main():
             runs = setup(B, a.T, g, a.envelope, a.histogram or a.predict, a.lqg)
             if a.predict:
                 if not a.histogram:       # the yardsticks of the prediction only, not the torch routes to the histogram
-                    runs = {k: f for k, f in runs.items() if k in ("A", "B_stats", "B_env", "H", "L_plain", "L_noise")}
+                    runs = {k: f for k, f in runs.items() if k in ("A", "B_stats", "B_noise", "B_env", "H", "L_plain", "L_noise")}
                 runs.update(setup_predict(a.T, g))
+            if a.filter:
+                if not a.predict:
+                    runs.update(setup_predict(a.T, g, torch_route=False))
+                filter_runs, host_ms = setup_filter(a.T, g)
+                runs.update(filter_runs)
         except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
             rec["refused"] = "allocation refused: %s" % str(e).split("\n")[0]
             out["sizes"].append(rec)
@@ -407,6 +467,13 @@ def main():
                                   B_noise_ms=med["B_noise"], L_noise_over_B_noise=round(med["L_noise"] / med["B_noise"], 4),
                                   L_plain_over_B_stats=round(med["L_plain"] / med["B_stats"], 4),
                                   spread_rel={k: sp(k) for k in ("L_plain", "L_noise", "B_stats", "B_noise")})
+            if a.filter:
+                sp = lambda k: round((max(ms[k]) - min(ms[k])) / med[k], 4)
+                ns = (1, 64, 1024)
+                rec["filter"] = dict(G_ms={"G_%d" % n: med["G_%d" % n] for n in ns}, P_ms={"P_%d" % n: med["P_%d" % n] for n in ns},
+                                     G_over_P={n: round(med["G_%d" % n] / med["P_%d" % n], 4) for n in ns},
+                                     host_one_optimum_ms=round(host_ms, 3), host_over_G_1=round(host_ms / med["G_1"], 1),
+                                     spread_rel={k: sp(k) for n in ns for k in ("G_%d" % n, "P_%d" % n)})
             if a.envelope:
                 E = med["E_traj"] + med["E_reduce"]
                 rec["envelope"] = dict(E_ms=round(E, 4), B_env_over_E=round(med["B_env"] / E, 4),
