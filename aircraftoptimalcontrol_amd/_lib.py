@@ -20,6 +20,7 @@ AOC_HIST_NCH, AOC_HIST_NBIN = 8, 64   # channels (dx[0..5], du[0..1]) and bins p
 AOC_COV_NREC = 32    # doubles per (optimum, sample) record of aoc_track_covariance
 AOC_LQG_NSTAT = 12   # estimation-error statistics per member of aoc_track_ensemble_lqg
 AOC_FILT_NREC = 42   # doubles per (optimum, sample) covariance record of aoc_filter_gains: upper triangles of P^- and P^+
+AOC_LQGCOV_NREC = 96 # doubles per (optimum, sample) record of aoc_track_covariance_lqg
 AOC_ABI_VERSION = 5   # include/aoc.h: the revision this binding (struct layouts, argument lists) is written against
 
 # status flags (include/aoc.h)
@@ -134,6 +135,8 @@ SYMBOLS = {
     "aoc_track_ensemble_lqg": (C.c_int, [_P, _I, _I] + [_P] * 15 + [_Z]),
     "aoc_filter_gains_scratch_bytes": (_Z, [_I, _I]),
     "aoc_filter_gains": (C.c_int, [_P, _I] + [_P] * 4 + [_I] + [_P] * 4 + [_Z]),
+    "aoc_track_covariance_lqg_scratch_bytes": (_Z, [_I, _I]),
+    "aoc_track_covariance_lqg": (C.c_int, [_P, _I] + [_P] * 10 + [_Z]),
     "aoc_traj_cost_f32": (C.c_int, [_P] * 5),
     "aoc_initial_trajectory_f32": (C.c_int, [_P, _D, _D, _P, _P, _P]),
     "aoc_rollout_cost_f32": (C.c_int, [_P] * 9),

@@ -988,6 +988,7 @@ HIST_NBIN = _lib.AOC_HIST_NBIN     # bins per (optimum, sample, channel)
 COV_NREC = _lib.AOC_COV_NREC       # doubles per (optimum, sample) record of aoc_track_covariance
 LQG_NSTAT = _lib.AOC_LQG_NSTAT     # estimation-error statistics per member of aoc_track_ensemble_lqg
 FILT_NREC = _lib.AOC_FILT_NREC     # doubles per (optimum, sample) covariance record of aoc_filter_gains
+LQGCOV_NREC = _lib.AOC_LQGCOV_NREC # doubles per (optimum, sample) record of aoc_track_covariance_lqg
 # the record (include/aoc.h): n | min dx | max dx | min du | max du | sum dx | sum dx_i dx_j (upper triangle, row by row)
 _ENV_MIN = np.r_[1:7, 13:15]
 _ENV_MAX = np.r_[7:13, 15:17]
@@ -1249,6 +1250,121 @@ def predict_covariance(problem, xx_opt, uu_opt, KK=None, mean0=None, Sigma0=None
     return [_covariance_dict(r) for r in raw], status
 
 
+def lqg_covariance_moments(raw):
+    """Records (T, 96) of aoc_track_covariance_lqg -> dict(mean_dx (6,T), cov_dx (6,6,T), mean_e (6,T), cov_e (6,6,T),
+    cov_dx_e (6,6,T) with [i,j] = cov(dx_i, e_j), cov_xhat (6,6,T) = X - C - C^T + E, the covariance of the estimate e^+
+    (formed here), mean_du (2,T), cov_du (2,2,T), raw): what linear theory predicts for the LQG loop, e = dx - e^+ the
+    posterior estimation error (sample T-1 of the input moments is 0: there is no input).  NumPy only, needs no GPU."""
+    raw = np.asarray(raw, dtype=np.float64)
+    if raw.ndim != 2 or raw.shape[1] != LQGCOV_NREC:
+        raise ValueError("records (T, %d) expected, got %s" % (LQGCOV_NREC, raw.shape))
+    T = raw.shape[0]
+    X, E = np.empty((T, 6, 6)), np.empty((T, 6, 6))
+    for M, o in ((X, 12), (E, 33)):
+        M[:, _ENV_TRI[0], _ENV_TRI[1]] = raw[:, o:o + 21]
+        M[:, _ENV_TRI[1], _ENV_TRI[0]] = raw[:, o:o + 21]
+    Cx = raw[:, 54:90].reshape(T, 6, 6)
+    cu = np.empty((T, 2, 2))
+    cu[:, 0, 0], cu[:, 0, 1], cu[:, 1, 0], cu[:, 1, 1] = raw[:, 92], raw[:, 93], raw[:, 93], raw[:, 94]
+    tm = lambda a: np.ascontiguousarray(a.transpose(1, 2, 0))
+    return dict(mean_dx=np.ascontiguousarray(raw[:, 0:6].T), cov_dx=tm(X), mean_e=np.ascontiguousarray(raw[:, 6:12].T),
+                cov_e=tm(E), cov_dx_e=tm(Cx), cov_xhat=tm(X - Cx - Cx.transpose(0, 2, 1) + E),
+                mean_du=np.ascontiguousarray(raw[:, 90:92].T), cov_du=tm(cu), raw=raw)
+
+
+def _rows6(a, n_opt, name):
+    """None, (6,) or (n_opt,6) -> (n_opt,6) contiguous, or None"""
+    if a is None:
+        return None
+    a = np.asarray(a, dtype=np.float64)
+    a = np.broadcast_to(a, (n_opt, 6)) if a.ndim == 1 else a
+    if a.shape != (n_opt, 6):
+        raise ValueError("%s must be (6,) or (n_opt,6) with n_opt = %d, got %s" % (name, n_opt, a.shape))
+    return np.ascontiguousarray(a)
+
+
+def _filter_to_device(filter, n_opt, T, dev):
+    """L (6,6,T) or (n_opt,6,6,T) -> the device array [n_opt][T][36] of aoc_track_ensemble_lqg / aoc_track_covariance_lqg"""
+    Lf = np.asarray(filter, dtype=np.float64)
+    Lf = Lf[None] if Lf.ndim == 3 else Lf
+    if Lf.shape != (n_opt, 6, 6, T):
+        raise ValueError("filter must be (6,6,T) or (n_opt,6,6,T) = %s, got %s" % ((n_opt, 6, 6, T), Lf.shape))
+    return _torch().from_numpy(np.ascontiguousarray(Lf.reshape(n_opt, 36, T).transpose(0, 2, 1))).to(dev)
+
+
+def _predict_covariance_lqg(problem, nominal, filt_d, n_opt, mean0, ehat0, Sigma0, sigma, rho):
+    """aoc_track_covariance_lqg on a device `nominal` (n_opt,T,20) and device gains (n_opt,T,36), on the current stream ->
+    records (n_opt,T,96) numpy, status (n_opt,)"""
+    torch = _torch()
+    dev, T = problem.device, problem.T
+    m0, e0 = _rows6(mean0, n_opt, "mean0"), _rows6(ehat0, n_opt, "ehat0")
+    m0 = _dev_f64(m0, dev) if m0 is not None else None
+    e0 = _dev_f64(e0, dev) if e0 is not None else None
+    S0 = _dev_f64(_sym_upper(Sigma0, n_opt), dev) if Sigma0 is not None else None
+    nz = None
+    if sigma is not None:
+        nz = _lib.MpcNoise(0, 0, 0, (C.c_double * 6)(*np.asarray(sigma, dtype=np.float64).reshape(6).tolist()))
+    rho_c = None
+    if rho is not None:
+        rho_c = (C.c_double * 6)(*np.asarray(rho, dtype=np.float64).reshape(6).tolist())
+    pred = torch.empty((n_opt, T, LQGCOV_NREC), dtype=torch.float64, device=dev)
+    status = torch.zeros(n_opt, dtype=torch.int32, device=dev)
+    nbytes = int(lib().aoc_track_covariance_lqg_scratch_bytes(n_opt, T))
+    scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    p = problem.c_problem(n_opt)
+    check(lib().aoc_track_covariance_lqg(C.byref(p), n_opt, _ptr(nominal), _ptr(filt_d), _ptr(m0), _ptr(e0), _ptr(S0),
+                                         C.byref(nz) if nz is not None else None, rho_c, _ptr(pred), _ptr(status),
+                                         _ptr(scratch), nbytes), "aoc_track_covariance_lqg")
+    return pred.cpu().numpy(), status.cpu().numpy()
+
+
+def predict_covariance_lqg(problem, xx_opt, uu_opt, filter, KK=None, mean0=None, ehat0=None, Sigma0=None, sigma=None,
+                           rho=None, measured=None):
+    """What linear theory predicts for the LQG loop of track_ensemble(filter=) about each optimum (aoc_track_covariance_lqg):
+    the joint mean and covariance of dx = x - x_opt and of the posterior estimation error e = dx - e^+ at every sample, and
+    the moments of du, for ANY gains L — the recursion of include/aoc.h.  xx_opt (6,T) or (n_opt,6,T), uu_opt likewise;
+    filter: L (6,6,T) or (n_opt,6,6,T), or "device": the gains of aoc_filter_gains on the same stream, which do not visit
+    the host — Sigma0 (required then), sigma, rho (required then) and `measured` are used as filter_gains_device uses them.
+    KK=None: gains from tracking_gains; mean0, ehat0 (6,) or (n_opt,6): the mean of dx_0 and the prior estimate, None = 0;
+    Sigma0 (6,6) or (n_opt,6,6), symmetric: the covariance of dx_0 (and of the prior error), None = 0; sigma, rho (6,): the
+    std of the disturbance and of the measurement noise, None = 0.
+    Returns (list per optimum of lqg_covariance_moments' dict, status (n_opt,))."""
+    device_gains = isinstance(filter, str)
+    if filter is None:
+        raise ValueError("filter= is required: L (6,6,T) or (n_opt,6,6,T), or \"device\"")
+    if device_gains:
+        if filter != "device":
+            raise ValueError('filter=%r: the only name is "device"' % (filter,))
+        if Sigma0 is None or rho is None:
+            raise ValueError('filter="device" needs Sigma0= (the covariance of the prior estimate\'s error) and rho=')
+        mask = _measured_mask(measured)
+    elif measured is not None:
+        raise ValueError('measured= goes with filter="device"')
+    xo, uo = np.asarray(xx_opt, dtype=np.float64), np.asarray(uu_opt, dtype=np.float64)
+    if xo.ndim == 2:
+        xo, uo = xo[None], uo[None]
+    n_opt, T = xo.shape[0], problem.T
+    if xo.shape != (n_opt, 6, T) or uo.shape != (n_opt, 2, T):
+        raise ValueError("xx_opt must be (6,T) or (n_opt,6,T) with T = %d, uu_opt likewise" % T)
+    if not device_gains:
+        Lf = np.asarray(filter, dtype=np.float64)
+        if (Lf[None] if Lf.ndim == 3 else Lf).shape != (n_opt, 6, 6, T):
+            raise ValueError("filter must be (6,6,T) or (n_opt,6,6,T) = %s, got %s" % ((n_opt, 6, 6, T), Lf.shape))
+    torch = _torch()
+    if KK is None:
+        KK, _ = tracking_gains(problem, xo, uo)
+    else:
+        KK = np.asarray(KK, dtype=np.float64)
+        KK = KK[None] if KK.ndim == 3 else KK
+    nominal = torch.from_numpy(ensemble_nominal(xo, uo, KK)).to(problem.device)
+    if device_gains:
+        filt_d, _, _ = _filter_gains_device(problem, nominal, n_opt, Sigma0, sigma, rho, mask, False)
+    else:
+        filt_d = _filter_to_device(filter, n_opt, T, problem.device)
+    raw, status = _predict_covariance_lqg(problem, nominal, filt_d, n_opt, mean0, ehat0, Sigma0, sigma, rho)
+    return [lqg_covariance_moments(r) for r in raw], status
+
+
 def filter_gains(problem, xx_opt, uu_opt, Sigma0, sigma, rho, jac=None):
     """Gains of the Kalman filter linearised about ONE optimum, for track_ensemble(rho=, filter=): the recursion in NumPy,
         L_t = P^-_t (P^-_t + V)^-1,   P^+_t = (I - L_t) P^-_t (I - L_t)^T + L_t V L_t^T   (Joseph form),
@@ -1362,7 +1478,7 @@ def _ens_summary(torch, v):
 def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, sigma=None, seed=20260405, first=0,
                    step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True, envelope=False,
                    quantiles=None, bins=None, predict=False, mean0=None, Sigma0=None, predict_k=6.0, rho=None, filter=None,
-                   ehat0=None, measured=None):
+                   ehat0=None, measured=None, predict_joint=False):
     """Closed-loop tracking ensemble about shared optima (aoc_track_ensemble): the loop of lqr_tracking.py:279-281 for B
     members, u_t = u_opt_t + K_t (x_t - x_opt_t), x_{t+1} = step(x_t, u_t) + d_t, reduced to per-member statistics on
     the device; the optimum and its gains are stored once per optimum, not once per member.
@@ -1409,8 +1525,16 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     computed on the device by ONE call and handed over as they lie — nothing of L visits the host.  The filter is built on
     Sigma0 (6,6) / (n_opt,6,6), the covariance of the prior estimate's error (required: ValueError without it), the call's
     sigma and rho (required), and measures the channels `measured` (a sequence of indices; None = all; filter_gains_device).
-    The members' measurement noise is still drawn in all six channels with rho.  Adds `filter_status` (n_opt,)."""
+    The members' measurement noise is still drawn in all six channels with rho.  Adds `filter_status` (n_opt,).
+    predict_joint=True (with filter=; aoc_track_covariance_lqg on the same gains; every other output keeps its bits): also
+    `predicted_joint`, per optimum what linear theory gives for THIS loop — lqg_covariance_moments' dict, the joint moments
+    of dx and of the estimation error e — and `predicted_joint_status` (n_opt,).  mean0 / Sigma0 = None: the population
+    moments of each group's own initial deviations, as for predict=True (with filter="device", Sigma0 is the filter's
+    prior as well).  ValueError without filter=."""
     lqg = filter is not None
+    if predict_joint and not lqg:
+        raise ValueError("predict_joint=True goes with filter= (the prediction of the LQG loop); predict=True is the "
+                         "prediction of the loop that feeds back the true state")
     device_gains = isinstance(filter, str)
     if device_gains:
         if filter != "device":
@@ -1517,11 +1641,7 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
         if device_gains:
             filt_d, _, filt_status = _filter_gains_device(problem, nominal, n_opt, Sigma0, sigma, rho, mask, False)
         else:
-            Lf = np.asarray(filter, dtype=np.float64)
-            Lf = Lf[None] if Lf.ndim == 3 else Lf
-            if Lf.shape != (n_opt, 6, 6, T):
-                raise ValueError("filter must be (6,6,T) or (n_opt,6,6,T) = %s, got %s" % ((n_opt, 6, 6, T), Lf.shape))
-            filt_d = torch.from_numpy(np.ascontiguousarray(Lf.reshape(n_opt, 36, T).transpose(0, 2, 1))).to(dev)   # [opt][t][36]
+            filt_d = _filter_to_device(filter, n_opt, T, dev)   # [opt][t][36]
         e0_d = None
         if ehat0 is not None:
             e0 = np.asarray(ehat0, dtype=np.float64)
@@ -1545,6 +1665,14 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
                                            _ptr(xr), _ptr(ur), _ptr(xh), _ptr(ds), _ptr(ms), _ptr(stats), _ptr(est_stats),
                                            _ptr(status), _ptr(scratch), nbytes), "aoc_track_ensemble_lqg")
         del scratch
+        if predict_joint:
+            dx0 = x0 - xo[group, :, 0]
+            jm0 = mean0 if mean0 is not None else np.stack([dx0[group == k].mean(axis=0) for k in range(n_opt)])
+            jS0 = Sigma0
+            if jS0 is None:
+                jS0 = np.stack([np.cov(dx0[group == k].T, bias=True).reshape(6, 6) for k in range(n_opt)])
+                jS0 = 0.5 * (jS0 + jS0.transpose(0, 2, 1))
+            joint_raw, joint_status = _predict_covariance_lqg(problem, nominal, filt_d, n_opt, jm0, ehat0, jS0, sigma, rho)
     elif not envelope and not hist:
         check(lib().aoc_track_ensemble(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp,
                                        _ptr(xr), _ptr(ur), _ptr(ds), _ptr(stats), _ptr(status)), "aoc_track_ensemble")
@@ -1564,6 +1692,8 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
         out.update(est_stats=es, max_e=es[:, 0:6], sum_e2=es[:, 6:12])
         if device_gains:
             out["filter_status"] = filt_status.cpu().numpy()
+        if predict_joint:
+            out.update(predicted_joint=[lqg_covariance_moments(r) for r in joint_raw], predicted_joint_status=joint_status)
     if envelope:
         out["envelope"] = [_envelope_dict(r) for r in env.cpu().numpy()]
     if predict:

@@ -575,6 +575,18 @@ int aoc_filter_gains(const aoc_problem* p, int32_t n_opt, const double* nominal,
     return aoc64::api_filter_gains(p, n_opt, nominal, Sigma0, noise, rho, measured, filter, cov, status, scratch, scratch_bytes);
 }
 
+size_t aoc_track_covariance_lqg_scratch_bytes(int32_t n_opt, int32_t T) {
+    return aoc64::track_covariance_lqg_scratch_bytes(n_opt, T);
+}
+
+int aoc_track_covariance_lqg(const aoc_problem* p, int32_t n_opt, const double* nominal, const double* filter,
+                             const double* mean0, const double* ehat0, const double* Sigma0, const aoc_mpc_noise* noise,
+                             const double* rho, double* pred, int32_t* status, void* scratch, size_t scratch_bytes) {
+    static_assert(aoc64::LQC_NREC == AOC_LQGCOV_NREC, "joint prediction record of the kernel and of the header");
+    return aoc64::api_track_covariance_lqg(p, n_opt, nominal, filter, mean0, ehat0, Sigma0, noise, rho, pred, status, scratch,
+                                           scratch_bytes);
+}
+
 // ---- float32 arithmetic (aoc32): every array, the reference curves and the workspace are float32 ------
 int aoc_traj_cost_f32(const aoc_problem* p, const float* x, const float* u, const float* x0, float* J) {
     if (p && p->ref_per_traj) return einval("aoc_traj_cost_f32: per-trajectory reference curves exist in the fp64 build only");

@@ -24,5 +24,6 @@ namespace AOC_ARITH_NS {
 #include "passes/covariance.inc" // likewise (the nominal's record is that of ensemble.inc)
 #include "passes/lqg.inc"        // launch function only: k_cov_stage of covariance.inc, then the EST instance of ensemble.inc
 #include "passes/filter.inc"     // the filter's gains: k_cov_stage without B K, then a chain kernel of its own
+#include "passes/lqgcov.inc"     // the joint (dx, e) prediction of the LQG loop: both k_cov_stage instances, then a chain kernel
 
 }  // namespace AOC_ARITH_NS

@@ -7,7 +7,8 @@ JSON line.
     python examples/run_tracking_ensemble.py [--data Data] [--members 65536] [--sigma 1e-3 1e-3 1e-2 1e-4 1e-3 1e-4]
                                              [--delta 0.3 0.3 0.5 0.05 0.1 0.05] [--seed 1] [--dt 1e-3]
                                              [--envelope FILE.npz] [--quantiles FILE.npz [--q 0.05 0.5 0.95]]
-                                             [--predict FILE.npz] [--rho r0 r1 r2 r3 r4 r5 [--device-gains] [--measured c ...]]
+                                             [--predict FILE.npz] [--rho r0 r1 r2 r3 r4 r5 [--device-gains] [--measured c ...]
+                                                                   [--predict-joint FILE.npz]]
 
 --envelope FILE.npz: also reduce over the members at every sample on the device (the tube around the optimum) and save
 n (T,), min_dx / max_dx (6,T), min_du / max_du (2,T), mean_dx (6,T), cov_dx (6,6,T), raw (T,44); the JSON line then
@@ -27,6 +28,12 @@ squared estimation error.  Not together with --envelope, --quantiles or --predic
 --device-gains (takes effect only with --rho): the filter's gains are computed on the device (aoc_filter_gains) and handed to
 the ensemble as they lie, batch.track_ensemble(filter="device"); --measured c ...: the filter then measures these channels
 only (default: all six).  The JSON line then also carries "device_gains": true and "measured".
+--predict-joint FILE.npz (with --rho): also what linear theory predicts for THIS loop (aoc_track_covariance_lqg with the same
+gains, from the population moments of the initial perturbation, --sigma and --rho) and save mean_dx, mean_e (6,T), cov_dx,
+cov_e, cov_dx_e, cov_xhat (6,6,T), mean_du (2,T), cov_du (2,2,T), raw (T,96), status; the JSON line then carries
+"predict_joint": the file, and "predicted_rms_dx" / "predicted_rms_estimation_error" beside the sampled "rms_dx" /
+"rms_estimation_error": per channel the root of the mean over the samples of variance + mean^2.  The members' trajectories
+are then kept on the device to sample rms_dx (26 doubles per member and sample).
 """
 import argparse
 import json
@@ -53,10 +60,14 @@ def main():
     ap.add_argument("--rho", type=float, nargs=6, default=None, help="std of the measurement noise: a Kalman estimate in the loop")
     ap.add_argument("--device-gains", action="store_true", help="with --rho: the filter's gains from aoc_filter_gains")
     ap.add_argument("--measured", type=int, nargs="+", default=None, help="with --device-gains: the channels the filter measures")
+    ap.add_argument("--predict-joint", default=None, metavar="FILE.npz",
+                    help="with --rho: save the joint linear prediction of dx and of the estimation error")
     ap.add_argument("--q", type=float, nargs="+", default=[0.05, 0.5, 0.95], help="quantile levels of --quantiles")
     a = ap.parse_args()
     if a.rho is not None and (a.envelope or a.quantiles or a.predict):
         ap.error("--rho does not combine with --envelope, --quantiles or --predict")
+    if a.predict_joint is not None and a.rho is None:
+        ap.error("--predict-joint goes with --rho (the prediction of the loop with the estimator; --predict is the other one)")
     xx_opt = np.load(os.path.join(a.data, "xx_star.npy"))
     uu_opt = np.load(os.path.join(a.data, "uu_star.npy"))
     T = xx_opt.shape[1]
@@ -64,12 +75,14 @@ def main():
     bp = batch.BatchProblem(Q, R, QT, np.zeros((6, T)), np.zeros((2, T)), a.dt)
     delta = np.random.default_rng(a.seed).normal(size=(a.members, 6)) * np.asarray(a.delta)
     device_gains = a.rho is not None and a.device_gains
+    joint = dict(predict_joint=True, mean0=np.zeros(6), trajectories=True, to_host=False) if a.predict_joint is not None else {}
     if device_gains:
         r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, filter="device", rho=a.rho,
-                                 Sigma0=np.diag(np.asarray(a.delta) ** 2), measured=a.measured)
+                                 Sigma0=np.diag(np.asarray(a.delta) ** 2), measured=a.measured, **joint)
     elif a.rho is not None:
         L = batch.filter_gains(bp, xx_opt, uu_opt, np.diag(np.asarray(a.delta) ** 2), a.sigma, a.rho)[0]
-        r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, filter=L, rho=a.rho)
+        r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, filter=L, rho=a.rho,
+                                 Sigma0=np.diag(np.asarray(a.delta) ** 2) if joint else None, **joint)
     else:
         r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, envelope=a.envelope is not None,
                                  quantiles=a.q if a.quantiles is not None else None, predict=a.predict is not None,
@@ -80,6 +93,15 @@ def main():
                 max_dx=tolist(sm["max_dx"]), final_dx=tolist(sm["final_dx"]), cost=tolist(sm["cost"]))
     if a.rho is not None:
         line.update(rho=list(a.rho), rms_estimation_error=np.sqrt(r["sum_e2"].mean(axis=0) / T).tolist())
+    if a.predict_joint is not None:
+        pj = r["predicted_joint"][0]
+        np.savez(a.predict_joint, status=r["predicted_joint_status"][0], **pj)
+        import torch
+        dx = r["xx_reg"] - torch.from_numpy(xx_opt).to(r["xx_reg"].device)[None]
+        rms = lambda mean, cov: np.sqrt((np.einsum("iit->it", cov) + mean ** 2).mean(axis=1)).tolist()
+        line.update(predict_joint=a.predict_joint, rms_dx=torch.sqrt((dx * dx).mean(dim=(0, 2))).cpu().numpy().tolist(),
+                    predicted_rms_dx=rms(pj["mean_dx"], pj["cov_dx"]),
+                    predicted_rms_estimation_error=rms(pj["mean_e"], pj["cov_e"]))
     if device_gains:
         line.update(device_gains=True, measured=sorted(set(a.measured)) if a.measured is not None else list(range(6)))
     if a.envelope is not None:

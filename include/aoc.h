@@ -68,7 +68,9 @@ extern "C" {
  *      (still 5, an addition: aoc_track_ensemble_lqg, aoc_track_ensemble_lqg_scratch_bytes — no struct, argument list or
  *      size query of an existing entry changed)
  *      (still 5, an addition: aoc_filter_gains, aoc_filter_gains_scratch_bytes — no struct, argument list or size query of
- *      an existing entry changed) */
+ *      an existing entry changed)
+ *      (still 5, an addition: aoc_track_covariance_lqg, aoc_track_covariance_lqg_scratch_bytes — no struct, argument list or
+ *      size query of an existing entry changed) */
 #define AOC_ABI_VERSION 5
 
 #define AOC_TILE 64
@@ -715,6 +717,47 @@ size_t aoc_filter_gains_scratch_bytes(int32_t n_opt, int32_t T);
 int aoc_filter_gains(const aoc_problem *prob, int32_t n_opt, const double *nominal, const double *Sigma0,
                      const aoc_mpc_noise *noise, const double *rho, int32_t measured, double *filter, double *cov,
                      int32_t *status, void *scratch, size_t scratch_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * What LINEAR theory predicts for the loop of aoc_track_ensemble_lqg: the JOINT mean and covariance of dx = x - x_opt and of the
+ * posterior estimation error e_t = dx_t - e^+_t, for ANY gain sequence L — the Kalman gains of aoc_filter_gains, a detuned
+ * filter, unmeasured channels (columns of +0.0), L = 0.  With A_t, F_t = A_t + B_t K_t and c_t as defined for
+ * aoc_track_covariance, N_t = F_t - A_t, J_t = I - L_t, V = diag(rho^2), W = diag(sigma^2), the loop linearised about the
+ * optimum is  e_t = J_t eps_t - L_t v_t,  dx_{t+1} = F_t dx_t - N_t e_t + c_t + d_t,  eps_{t+1} = A_t e_t + d_t  (eps the
+ * prior error).  With m = E dx, mu = E e, X = cov(dx), E = cov(e), C = cov(dx, e) (C_ij = cov(dx_i, e_j), not symmetric):
+ *     start:        m_0 = mean0,  mu^-_0 = mean0 - ehat0,  X_0 = E^-_0 = C^-_0 = Sigma0
+ *     t = 0..T-1:   mu_t = J_t mu^-_t,   E_t = J_t E^-_t J_t^T + L_t V L_t^T (Joseph form),   C_t = C^-_t J_t^T
+ *     t <= T-2:     m_{t+1} = F_t m_t - N_t mu_t + c_t,   mu^-_{t+1} = A_t mu_t,
+ *                   X_{t+1} = F X F^T - F C N^T - N C^T F^T + N E N^T + W,   C^-_{t+1} = (F C - N E) A^T + W,
+ *                   E^-_{t+1} = A E A^T + W.
+ * When L is the Kalman gain of (Sigma0, sigma, rho) and ehat0 = mean0, E_t is P^+_t of aoc_filter_gains and C_t = E_t.
+ * prob, nominal, mean0, Sigma0, noise, status and the scratch rules: as for aoc_track_covariance.
+ * filter: DEVICE, fp64, [n_opt][T][36], L_t row-major: the array aoc_filter_gains writes and aoc_track_ensemble_lqg reads.
+ *   Not NULL.  ehat0: DEVICE, [n_opt][6], or NULL = 0.
+ * rho: HOST, 6 doubles >= 0 and finite, or NULL = 0; read without `noise`: only the standard deviations matter here.
+ * pred: DEVICE, fp64, [n_opt][T][AOC_LQGCOV_NREC].  Record of optimum k at sample t:
+ *     0-5    m_t              6-11   mu_t           12-32  upper triangle of X_t, row by row      33-53  that of E_t
+ *     54-89  C_t, row-major   90-91  K_t (m_t - mu_t), the mean of du
+ *     92-94  K_t (X_t - C_t - C_t^T + E_t) K_t^T, entries 00, 01, 11 (X - C - C^T + E is the covariance of e^+)      95  +0.0
+ *   Sample T-1 has no input: entries 90-94 are +0.0 there.  X and E are symmetric by construction (both halves are one
+ *   expression).  Every sum starts from +0.0: with Sigma0 = NULL, noise = NULL and rho = NULL the entries 12-89 and 92-94 are
+ *   exactly +0.0 at every sample wherever the records are finite.
+ * status: as aoc_track_covariance; in addition AOC_ST_NAN if an entry of the optimum's `filter` is not finite.  Such an
+ *   optimum yields whatever the arithmetic gives and disturbs no other.
+ * scratch: at least aoc_track_covariance_lqg_scratch_bytes(n_opt, T) bytes (0 for a geometry the call refuses).
+ * AOC_EINVAL with the reason, before anything touches a device: prob, nominal, filter or pred NULL; n_opt < 1; T < 3; a
+ * negative or non-finite rho or sigma; scratch NULL, misaligned or too small.
+ * Three kernels on prob->stream: the first kernel of aoc_track_covariance with and without its B K term (F_t, c_t, K_t and
+ * A_t, into the two halves of scratch), then one wavefront per optimum for the recursion, whose lanes own the entries of X, C
+ * and E.  No atomics, a fixed order: the same bits every run, and an optimum's record does not depend on n_opt or on its
+ * position in the call.
+ * --------------------------------------------------------------------------------------------- */
+#define AOC_LQGCOV_NREC 96
+size_t aoc_track_covariance_lqg_scratch_bytes(int32_t n_opt, int32_t T);
+int aoc_track_covariance_lqg(const aoc_problem *prob, int32_t n_opt, const double *nominal, const double *filter,
+                             const double *mean0, const double *ehat0, const double *Sigma0,
+                             const aoc_mpc_noise *noise, const double *rho, double *pred, int32_t *status,
+                             void *scratch, size_t scratch_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * float32 arithmetic (BASELINE.json configs[2]: "fp32 with tolerance sweep").

@@ -46,6 +46,14 @@ and reports L_noise / B_noise and L_plain / B_stats of the same run.
   P_n        aoc_track_covariance for n optima in the same run: the same chain without the downdates
 and reports G_n / P_n, and the host recursion batch.filter_gains for ONE optimum with the Jacobians already in hand (wall
 clock, the median of three).
+--joint adds the joint (dx, e) covariance prediction of the LQG loop (aoc_track_covariance_lqg, 96 numbers per sample and
+optimum, all three kernels), for n_opt = 1, 64 and 1024 windows of the optimum as --predict takes them, the gains those of
+aoc_filter_gains (prior diag(DELTA_SCALE^2), rho = 0.1 of it, all six channels), the prediction from the same prior:
+  J_n        aoc_track_covariance_lqg for n optima, the gains already on the device
+  JG_n       aoc_filter_gains, then aoc_track_covariance_lqg, on the same stream
+  TJ_n       the best torch route to the same 96 numbers: Jacobians from aoc_step_batch for all (optimum, stage) pairs, then a
+             stage loop of batched fp64 matmuls on the device
+and reports J_n / P_n and J_n / G_n against the chains of --predict and --filter of the same run (give them too).
 The optimum is the g4 fixture's (T = 1000; --T cuts it), the members are seeded perturbations of its first sample.
 Profiler off: HIP events around at least --seconds of back-to-back launches per variant, after a warm-up of every variant;
 the variants take turns inside each of --repeats rounds, so that a drift of the machine hits all of them.  One JSON line:
@@ -358,6 +366,111 @@ def setup_predict(T, g, sizes=(1, 64, 1024), torch_route=True):
     return runs
 
 
+def setup_joint(T, g, sizes=(1, 64, 1024), torch_route=True):
+    """Launch closures of the joint prediction for each n_opt in `sizes`: with the gains in hand, with aoc_filter_gains in front,
+    and of the torch route to the same records."""
+    import torch
+    from aircraftoptimalcontrol_amd import _lib, batch
+    from aircraftoptimalcontrol_amd.batch import _ptr, check, lib
+    dev = torch.device("cuda:0")
+    Tg = g["xx_opt"].shape[1]
+    bp = batch.BatchProblem(g["QQt"], g["RRt"], g["QQT"], np.zeros((6, T)), np.zeros((2, T)), float(g["dt"]), device=dev)
+    nz = _lib.MpcNoise(20261016, 0, 0, (C.c_double * 6)(*SIGMA.tolist()))
+    rho = 0.1 * DELTA_SCALE
+    rho_c = (C.c_double * 6)(*rho.tolist())
+    S0 = torch.from_numpy(np.diag(DELTA_SCALE ** 2)[np.triu_indices(6)]).to(dev)
+    NREC = _lib.AOC_LQGCOV_NREC
+    runs = {}
+    for n in sizes:
+        off = [(k % max(1, Tg - T + 1)) for k in range(n)]
+        xo = np.stack([g["xx_opt"][:, o:o + T] for o in off])
+        uo = np.stack([g["uu_opt"][:, o:o + T] for o in off])
+        KK = np.stack([g["KK"][:, :, o:o + T] for o in off])
+        nominal = torch.from_numpy(batch.ensemble_nominal(xo, uo, KK)).to(dev)
+        Sig = S0.repeat(n, 1).contiguous()
+        filt = torch.empty((n, T, 36), dtype=torch.float64, device=dev)
+        pred = torch.empty((n, T, NREC), dtype=torch.float64, device=dev)
+        gbytes = int(lib().aoc_filter_gains_scratch_bytes(n, T))
+        nbytes = int(lib().aoc_track_covariance_lqg_scratch_bytes(n, T))
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        p = bp.c_problem(n)
+
+        def run_G(p=p, n=n, nominal=nominal, Sig=Sig, filt=filt, scratch=scratch, gbytes=gbytes):
+            check(lib().aoc_filter_gains(C.byref(p), n, _ptr(nominal), _ptr(Sig), C.byref(nz), rho_c, 63, _ptr(filt), None, None,
+                                         _ptr(scratch), gbytes), "aoc_filter_gains")
+
+        def run_J(p=p, n=n, nominal=nominal, Sig=Sig, filt=filt, pred=pred, scratch=scratch, nbytes=nbytes):
+            check(lib().aoc_track_covariance_lqg(C.byref(p), n, _ptr(nominal), _ptr(filt), None, None, _ptr(Sig), C.byref(nz), rho_c,
+                                                 _ptr(pred), None, _ptr(scratch), nbytes), "aoc_track_covariance_lqg")
+
+        def run_JG(run_G=run_G, run_J=run_J):
+            run_G()
+            run_J()
+
+        run_G()
+        runs["J_%d" % n], runs["JG_%d" % n] = run_J, run_JG
+        if not torch_route:
+            continue
+        # the torch route: one aoc_step_batch over all pairs, then T dependent stages of batched 6x6 products
+        xs = nominal[:, :, 0:6].reshape(-1, 6).contiguous()
+        us = nominal[:, :, 6:8].reshape(-1, 2).contiguous()
+        Kt = nominal[:, :, 8:20].reshape(n, T, 2, 6)
+        xp = torch.empty((n * T, 6), dtype=torch.float64, device=dev)
+        fx = torch.empty((n * T, 6, 6), dtype=torch.float64, device=dev)
+        fu = torch.empty((n * T, 2, 6), dtype=torch.float64, device=dev)
+        W = torch.diag(torch.from_numpy(SIGMA ** 2)).to(dev)
+        V = torch.diag(torch.from_numpy(rho ** 2)).to(dev)
+        I6 = torch.eye(6, dtype=torch.float64, device=dev)
+        iu = torch.triu_indices(6, 6, device=dev)
+        P0 = torch.zeros((n, 6, 6), dtype=torch.float64, device=dev)
+        P0[:, iu[0], iu[1]] = Sig
+        P0 = P0 + P0.transpose(1, 2) - torch.diag_embed(torch.diagonal(P0, dim1=1, dim2=2))
+        out = torch.zeros((n, T, NREC), dtype=torch.float64, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+        def run_TJ(n=n, xs=xs, us=us, Kt=Kt, xp=xp, fx=fx, fu=fu, P0=P0, out=out, nominal=nominal, filt=filt):
+            check(lib().aoc_step_batch(C.byref(bp.model), n * T, _ptr(xs), _ptr(us), None, _ptr(xp), _ptr(fx), _ptr(fu), None, None,
+                                       None, st), "aoc_step_batch")
+            A = fx.view(n, T, 6, 6).transpose(2, 3)
+            N = torch.matmul(fu.view(n, T, 2, 6).transpose(2, 3), Kt)                   # (n,T,6,6)
+            F = A + N
+            Lt = filt.view(n, T, 6, 6)
+            J = I6 - Lt
+            LVL = torch.matmul(torch.matmul(Lt, V), Lt.transpose(2, 3))                 # off the chain, all samples at once
+            c = xp.view(n, T, 6)[:, :T - 1] - nominal[:, 1:, 0:6]
+            z = torch.zeros((n, 6, 1), dtype=torch.float64, device=dev)
+            X, Cm, Em, m, mu = P0, P0, P0, z, z
+            for t in range(T):
+                Jt = J[:, t]
+                mu = torch.matmul(Jt, mu)
+                E = torch.matmul(torch.matmul(Jt, Em), Jt.transpose(1, 2)) + LVL[:, t]
+                Cx = torch.matmul(Cm, Jt.transpose(1, 2))
+                out[:, t, 0:6], out[:, t, 6:12] = m[:, :, 0], mu[:, :, 0]
+                out[:, t, 12:33], out[:, t, 33:54] = X[:, iu[0], iu[1]], E[:, iu[0], iu[1]]
+                out[:, t, 54:90] = Cx.reshape(n, 36)
+                if t == T - 1:
+                    break
+                K = Kt[:, t]
+                out[:, t, 90:92] = torch.matmul(K, m - mu)[:, :, 0]
+                KHK = torch.matmul(torch.matmul(K, X - Cx - Cx.transpose(1, 2) + E), K.transpose(1, 2))
+                out[:, t, 92], out[:, t, 93], out[:, t, 94] = KHK[:, 0, 0], KHK[:, 0, 1], KHK[:, 1, 1]
+                Ft, Nt, At = F[:, t], N[:, t], A[:, t]
+                Y1 = torch.matmul(Ft, X) - torch.matmul(Nt, Cx.transpose(1, 2))
+                Y2 = torch.matmul(Ft, Cx) - torch.matmul(Nt, E)
+                m = torch.matmul(Ft, m) - torch.matmul(Nt, mu) + c[:, t].unsqueeze(2)
+                mu = torch.matmul(At, mu)
+                X = torch.matmul(Y1, Ft.transpose(1, 2)) - torch.matmul(Y2, Nt.transpose(1, 2)) + W
+                Cm = torch.matmul(Y2, At.transpose(1, 2)) + W
+                Em = torch.matmul(torch.matmul(At, E), At.transpose(1, 2)) + W
+            return out
+
+        run_J(); want = run_TJ(); torch.cuda.synchronize()                                # the two routes agree before either is timed
+        scale = want.abs().amax(dim=(0, 1)).clamp(min=1e-300)
+        assert bool((((pred - want).abs() / scale) <= 1e-8).all()), "J and TJ disagree"
+        runs["TJ_%d" % n] = run_TJ
+    return runs
+
+
 def timed(fn, seconds):
     """ms per call over at least `seconds` of back-to-back launches (HIP events; one launch first sizes the window)"""
     import torch
@@ -388,7 +501,7 @@ def kernel_times(d):
     out = collections.OrderedDict()
     for name, t0, t1, grid in sorted(rows, key=lambda r: r[1]):
         name = name.split("(")[0].replace("void ", "").replace("aoc64::", "")
-        if name.startswith(("k_track_", "k_envelope_", "k_histogram_", "k_cov_", "k_filter_")):
+        if name.startswith(("k_track_", "k_envelope_", "k_histogram_", "k_cov_", "k_filter_", "k_lqgcov_")):
             out.setdefault("%s grid=%s" % (name, grid), []).append(round((t1 - t0) / 1e6, 4))
     for k, v in out.items():
         print(json.dumps(dict(kernel=k, ms=v, median=float(np.median(v)), spread_rel=round((max(v) - min(v)) / float(np.median(v)), 4))))
@@ -408,6 +521,7 @@ def main():
     ap.add_argument("--predict", action="store_true", help="also time aoc_track_covariance for 1, 64 and 1024 optima")
     ap.add_argument("--lqg", action="store_true", help="also time aoc_track_ensemble_lqg, statistics only, with and without draws")
     ap.add_argument("--filter", action="store_true", help="also time aoc_filter_gains for 1, 64 and 1024 optima")
+    ap.add_argument("--joint", action="store_true", help="also time aoc_track_covariance_lqg for 1, 64 and 1024 optima")
     ap.add_argument("--hist-valu", type=int, default=0, help="vector instructions per stage of the histogram kernel (from the ISA)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -431,6 +545,8 @@ def main():
                     runs.update(setup_predict(a.T, g, torch_route=False))
                 filter_runs, host_ms = setup_filter(a.T, g)
                 runs.update(filter_runs)
+            if a.joint:
+                runs.update(setup_joint(a.T, g))
         except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
             rec["refused"] = "allocation refused: %s" % str(e).split("\n")[0]
             out["sizes"].append(rec)
@@ -474,6 +590,17 @@ def main():
                                      G_over_P={n: round(med["G_%d" % n] / med["P_%d" % n], 4) for n in ns},
                                      host_one_optimum_ms=round(host_ms, 3), host_over_G_1=round(host_ms / med["G_1"], 1),
                                      spread_rel={k: sp(k) for n in ns for k in ("G_%d" % n, "P_%d" % n)})
+            if a.joint:
+                sp = lambda k: round((max(ms[k]) - min(ms[k])) / med[k], 4)
+                ns = (1, 64, 1024)
+                rec["joint"] = dict(J_ms={"J_%d" % n: med["J_%d" % n] for n in ns}, JG_ms={"JG_%d" % n: med["JG_%d" % n] for n in ns},
+                                    TJ_ms={"TJ_%d" % n: med["TJ_%d" % n] for n in ns},
+                                    TJ_over_J={n: round(med["TJ_%d" % n] / med["J_%d" % n], 1) for n in ns},
+                                    spread_rel={k: sp(k) for n in ns for k in ("J_%d" % n, "JG_%d" % n)})
+                if "P_1" in med:
+                    rec["joint"]["J_over_P"] = {n: round(med["J_%d" % n] / med["P_%d" % n], 4) for n in ns}
+                if "G_1" in med:
+                    rec["joint"]["J_over_G"] = {n: round(med["J_%d" % n] / med["G_%d" % n], 4) for n in ns}
             if a.envelope:
                 E = med["E_traj"] + med["E_reduce"]
                 rec["envelope"] = dict(E_ms=round(E, 4), B_env_over_E=round(med["B_env"] / E, 4),
