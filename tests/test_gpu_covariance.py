@@ -23,6 +23,10 @@ REF_GAP = 2.14e-14
 TOL = 16 * REF_GAP
 SIZES_T = (3, 17, 33, 200)
 SIZES_N = (1, 3, 70)
+# the horizon edges, run at n_opt = 3 alone: T - 1 = 15 and 31 are the last record of a block of the 16-record prefetch (the
+# block behind it holds nothing), T = 18 puts one stage into the second block, T = 4 is the first horizon with an inner stage
+EDGE_T = (4, 16, 18, 32)
+EDGE_N = 3
 
 
 def jacobians(mdl, xo, uo):
@@ -130,15 +134,15 @@ def checker_records(jac, XO, KK, m0, S0, sigma, dtype=np.float64):
 
 def reference_gap(sizes_T=SIZES_T, sizes_n=SIZES_N):
     """The checker's own rounding: the largest scaled gap between numpy_covariance in fp64 and in np.longdouble over the
-    cases of test_parity_with_the_checker and test_a_nominal_that_is_not_a_rollout.  Needs no GPU."""
+    cases of test_parity_with_the_checker, test_parity_at_the_horizon_edges and test_a_nominal_that_is_not_a_rollout.  Needs
+    no GPU."""
     worst = 0.0
-    for T in sizes_T:
-        for n_opt in sizes_n:
-            XO, _, KK, jac = windows(n_opt, T)
-            for name in CASES:
-                m0, S0, sigma = case_args(name, n_opt)
-                worst = max(worst, scaled_gap(checker_records(jac, XO, KK, m0, S0, sigma),
-                                              checker_records(jac, XO, KK, m0, S0, sigma, np.longdouble)))
+    for T, n_opt in [(T, n) for T in sizes_T for n in sizes_n] + [(T, EDGE_N) for T in EDGE_T]:
+        XO, _, KK, jac = windows(n_opt, T)
+        for name in CASES:
+            m0, S0, sigma = case_args(name, n_opt)
+            worst = max(worst, scaled_gap(checker_records(jac, XO, KK, m0, S0, sigma),
+                                          checker_records(jac, XO, KK, m0, S0, sigma, np.longdouble)))
     xo, _, KK, jac = offset_nominal(33)
     for name in ("plain", "noise_moments"):
         m0, S0, sigma = case_args(name, 1)
@@ -156,11 +160,14 @@ def offset_nominal(T):
     return xo, uo, g["KK"][:, :, :T], jacobians(mdl, xo, uo)
 
 
-def _predict(g, XO, UO, KK, m0, S0, sigma):
+def _predict_on(bp, XO, UO, KK, m0, S0, sigma):
     from aircraftoptimalcontrol_amd import batch
-    bp = _problem(dict(g, xx_opt=XO[0]))
     pred, status = batch.predict_covariance(bp, XO, UO, KK=KK, mean0=m0, Sigma0=S0, sigma=sigma)
     return np.stack([p["raw"] for p in pred]), status, pred
+
+
+def _predict(g, XO, UO, KK, m0, S0, sigma):
+    return _predict_on(_problem(dict(g, xx_opt=XO[0])), XO, UO, KK, m0, S0, sigma)
 
 
 @pytest.mark.parametrize("n_opt", SIZES_N)
@@ -168,6 +175,16 @@ def _predict(g, XO, UO, KK, m0, S0, sigma):
 def test_parity_with_the_checker(T, n_opt):
     """Windows of g4 at offsets 5k; T = 3 is the shortest horizon the call takes, 17 and 33 end one sample behind a block of
     the 16-record prefetch, 70 optima are more wavefronts than one; with and without noise, with and without mean0 / Sigma0."""
+    _parity(T, n_opt)
+
+
+@pytest.mark.parametrize("T", EDGE_T)
+def test_parity_at_the_horizon_edges(T):
+    """The parity test at the horizons EDGE_T (see there) with three optima."""
+    _parity(T, EDGE_N)
+
+
+def _parity(T, n_opt):
     g = g4_jacobians()[0]
     XO, UO, KK, jac = windows(n_opt, T)
     for name in CASES:
@@ -202,6 +219,102 @@ def test_a_nominal_that_is_not_a_rollout():
         assert np.abs(got[0, 1:, 0:6]).max() > 1e-6
         if name == "plain":   # the defect itself is the plant's own arithmetic: exact
             assert np.array_equal(got[0, 1, 0:6], jac[2][0] - xo[:, 1])
+
+
+G13_K_SEED = 13
+G13_BOUND = 1e-12      # the gate of tests/test_gpu_parity.py test_step_batch_wide_angles_vs_golden on the same Jacobians
+
+
+def g13_optima(K=None):
+    """Three-sample optima on ALL the points of tests/golden/g13_step_wide.npz (216: angles over +-4 pi, up to 2^24, V from
+    0.05 to 300) at its dt: optimum i has x_opt_0 = x[i], u_0 = u_1 = u[i], x_opt_1 = x_opt_2 = xp[i] widened to fp64, and
+    the gains K (2,6) at every sample (None = 0).  The device's step is xp bit for bit (test_step_batch_wide_angles_vs_golden),
+    so c_0 = +0.0.  -> g, XO (n,6,3), UO (n,2,3), KK (n,2,6,3), A (n,6,6) and B (n,6,2) of stage 0 from the golden fx = A^T,
+    fu = B^T."""
+    g = load_golden("g13_step_wide")
+    xp = g["xp"].astype(np.float64)
+    n = xp.shape[0]
+    XO = np.stack([g["x"], xp, xp], axis=2)
+    UO = np.stack([g["u"]] * 3, axis=2)
+    KK = np.zeros((n, 2, 6, 3)) if K is None else np.broadcast_to(np.asarray(K)[None, :, :, None], (n, 2, 6, 3)).copy()
+    return g, XO, UO, KK, g["fx"].transpose(0, 2, 1), g["fu"].transpose(0, 2, 1)
+
+
+def g13_gains():
+    """the fixed gains of order one of the G13 tests, the same at every point"""
+    return np.random.default_rng(G13_K_SEED).normal(size=(2, 6))
+
+
+def g13_problem(g):
+    from aircraftoptimalcontrol_amd import batch
+    return batch.BatchProblem(np.eye(6), np.eye(2), np.eye(6), np.zeros((6, 3)), np.zeros((2, 3)), float(g["dt"]))
+
+
+def g13_gap(got, A, B, K=None):
+    """got (n,6,6) against A + B K formed in np.longdouble, per entry over |A_ij| + sum_r |B_ir K_rj| -> (the largest gap
+    over the entries whose scale is not 0, the point that sets it, its entry); an entry whose scale is 0 must be exactly
+    zero in `got` (asserted here: the sparsity of A and B)."""
+    Al, Bl = A.astype(np.longdouble), B.astype(np.longdouble)
+    Kl = np.zeros((2, 6), np.longdouble) if K is None else np.asarray(K).astype(np.longdouble)
+    want = Al + np.einsum("nir,rj->nij", Bl, Kl)
+    scale = (np.abs(Al) + np.einsum("nir,rj->nij", np.abs(Bl), np.abs(Kl))).astype(np.float64)
+    live = scale > 0
+    assert got.shape == scale.shape and not got[~live].any(), "an entry outside the sparsity of A + B K is not zero"
+    gap = np.zeros(scale.shape)
+    gap[live] = (np.abs(got.astype(np.longdouble) - want)[live]).astype(np.float64) / scale[live]
+    n, i, j = np.unravel_index(int(np.argmax(gap)), gap.shape)
+    return float(gap[n, i, j]), int(n), (int(i), int(j))
+
+
+def g13_report(what, gap, point, entry, g):
+    """print the largest gap and the point that sets it -> the record of it for AOC_TEST_RECORDS"""
+    x = g["x"][point]
+    print("%s: largest gap %.3g (bound %.3g) at point %d, entry %s: V = %.4g, theta = %.9g, gamma = %.9g"
+          % (what, gap, G13_BOUND, point, entry, x[2], x[3], x[5]))
+    return dict(what=what, gap=gap, bound=G13_BOUND, point=point, entry=list(entry), V=float(x[2]), theta=float(x[3]),
+                gamma=float(x[5]))
+
+
+@pytest.mark.parametrize("gains", [False, True], ids=["K0", "K13"])
+def test_stage_records_at_wide_angles(gains):
+    """k_cov_stage<true> off the g4 fixture, read through aoc_track_covariance alone: three-sample optima on all 216 points of
+    G13 (g13_optima), mean0 = e_j, no Sigma0, no noise, so the record of sample 1 holds m_1 = F[:, j] — one product with 1.0
+    and sums with +0.0: the device's own entry, unrounded.  With K = 0 that is A, with the seeded K of order one A + B K; both
+    against the golden fx, fu in np.longdouble, per entry over |A_ij| + sum_r |B_ir K_rj|, bound 1e-12 (the gate those
+    Jacobians already meet at aoc_step_batch); every entry outside the sparsity of A + B K is exactly zero.  status is
+    AOC_ST_VNONPOS exactly on the 30 optima whose xp[i, 2] <= 0 (stage 1 starts from V <= 0; their sample-1 record comes
+    from stage 0 and is compared like the rest).
+    Measured on an MI355X: K = 0: 3.92e-13; seeded K: 3.49e-13; both at entry (2, 2) of point 133, the cancelling entry that
+    sets the 3.9e-13 of aoc_step_batch; the parity gaps at EDGE_T stay below 3.0e-15."""
+    from test_gpu_parity import _record
+    K = g13_gains() if gains else None
+    g, XO, UO, KK, A, B = g13_optima(K)
+    n = XO.shape[0]
+    bp = g13_problem(g)
+    assert n == 216 and int((XO[:, 2, 1] <= 0).sum()) == 30
+    F = np.zeros((n, 6, 6))
+    for j in range(6):
+        got, status, _ = _predict_on(bp, XO, UO, KK, np.eye(6)[j], None, None)
+        F[:, :, j] = got[:, 1, 0:6]
+        assert np.array_equal(got[:, 0, 0:6], np.broadcast_to(np.eye(6)[j], (n, 6)))
+        assert np.array_equal(status, np.where(XO[:, 2, 1] <= 0, ST_VNONPOS, 0)), j
+    gap, point, entry = g13_gap(F, A, B, K)
+    rec = g13_report("F = A%s through aoc_track_covariance" % (" + B K" if gains else ""), gap, point, entry, g)
+    _record("g13_cov_stage_%s.json" % ("K13" if gains else "K0"), dict(points=n, **rec))
+    assert gap <= G13_BOUND, (gap, point, entry)
+
+
+def test_the_defect_at_wide_angles():
+    """mean0 = 0 and x_opt_1 moved off the rollout by DELTA_SCALE * 0.01 on all 216 points of G13: m_1 = c_0 = xp - x_opt_1
+    is the plant's own arithmetic, so it equals the host's fp64 difference bit for bit (the assertion of
+    test_a_nominal_that_is_not_a_rollout on g4), whatever the gains."""
+    g, XO, UO, KK, _, _ = g13_optima(g13_gains())
+    xp = XO[:, :, 2].copy()
+    XO[:, :, 1] = xp + DELTA_SCALE * 0.01
+    got, status, _ = _predict_on(g13_problem(g), XO, UO, KK, None, None, None)
+    assert np.array_equal(got[:, 1, 0:6], xp - XO[:, :, 1]) and np.abs(got[:, 1, 0:6]).max() > 1e-3
+    assert not got[:, 0, 0:6].any()
+    assert np.array_equal(status, np.where(XO[:, 2, 1] <= 0, ST_VNONPOS, 0))
 
 
 def test_exact_cases():

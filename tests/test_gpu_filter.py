@@ -21,6 +21,11 @@ gpu = pytest.mark.gpu
 ST_NAN, ST_VNONPOS, ST_SINGULAR = 1, 2, 4
 SIZES_T = (3, 17, 33, 200)
 SIZES_N = (1, 3, 65)
+# the horizon edges, run at n_opt = 3 alone: T - 1 = 15 and 31 are the last record of a block of the 16-record prefetch (the
+# block behind it holds nothing), T = 18 puts one stage into the second block, T = 4 is the first horizon with an inner stage
+EDGE_T = (4, 16, 18, 32)
+EDGE_N = 3
+MASK_T, MASK_N = 17, 3                        # test_every_mask: all 64 sets of measured channels, the full prior, SIGMA
 PRIORS = ("small", "unit", "full")            # diag((0.1 DELTA_SCALE)^2), diag(DELTA_SCALE^2), start_moments' full Sigma0
 NOISES = (True, False)                        # SIGMA, no disturbance
 MEASURED = ((0, 1, 2, 3, 4, 5), (0, 1, 4), (0,))
@@ -148,18 +153,25 @@ def all_cases():
     return [(p, n, m) for p in PRIORS for n in NOISES for m in MEASURED]
 
 
+def mask_channels(mask):
+    """the channels a 6-bit mask of aoc_filter_gains measures, ascending"""
+    return tuple(c for c in range(6) if mask >> c & 1)
+
+
 def reference_gap(sizes_T=SIZES_T, sizes_n=SIZES_N):
     """The reference's own rounding: the largest gaps between joseph_gains in fp64 and in np.longdouble over the cases of
-    test_parity_with_the_checker -> (cov, L, the case that sets cov, the case that sets L).  Needs no GPU."""
+    test_parity_with_the_checker, test_parity_at_the_horizon_edges and test_every_mask -> (cov, L, the case that sets cov,
+    the case that sets L).  Needs no GPU."""
     worst = [0.0, 0.0, None, None]
-    for T in sizes_T:
-        for k in sorted({k for n in sizes_n for k in checked_optima(n)}):
-            for case in all_cases():
-                gc, gl = gaps(reference(k, T, *case, dtype=np.float64), reference(k, T, *case))
-                if gc > worst[0]:
-                    worst[0], worst[2] = gc, (T, k) + case
-                if gl > worst[1]:
-                    worst[1], worst[3] = gl, (T, k) + case
+    runs = [(T, k, case) for T in sizes_T for k in sorted({k for n in sizes_n for k in checked_optima(n)}) for case in all_cases()]
+    runs += [(T, k, case) for T in EDGE_T for k in checked_optima(EDGE_N) for case in all_cases()]
+    runs += [(MASK_T, k, ("full", True, mask_channels(m))) for k in checked_optima(MASK_N) for m in range(64)]
+    for T, k, case in runs:
+        gc, gl = gaps(reference(k, T, *case, dtype=np.float64), reference(k, T, *case))
+        if gc > worst[0]:
+            worst[0], worst[2] = gc, (T, k) + case
+        if gl > worst[1]:
+            worst[1], worst[3] = gl, (T, k) + case
     return tuple(worst)
 
 
@@ -177,8 +189,28 @@ def test_parity_with_the_checker(T, n_opt):
     """Windows of g4 at offsets 5k; T = 3 is the shortest horizon the call takes, 17 and 33 end one sample behind a block of
     the 16-record prefetch, 65 optima are more wavefronts than one; three priors, with and without disturbance, all six
     channels, {0, 1, 4} and {0} measured.  Every unmeasured column of L is exactly +0.0."""
+    _parity(T, n_opt, all_cases())
+
+
+@gpu
+@pytest.mark.parametrize("T", EDGE_T)
+def test_parity_at_the_horizon_edges(T):
+    """The parity test at the horizons EDGE_T (see there) with three optima."""
+    _parity(T, EDGE_N, all_cases())
+
+
+@gpu
+def test_every_mask():
+    """All 64 sets of measured channels, T = 17, three optima, the full prior, SIGMA: the cross-lane pivots of the measurement
+    update run in every order the mask can give them.  The gates of the parity test; every unmeasured column of L is exactly
+    +0.0 (all of L with nothing measured) and status is clean.  Measured on an MI355X, this test and the horizon edges
+    together: covariances at most 2.7e-15, gains 2.0e-15."""
+    _parity(MASK_T, MASK_N, [("full", True, mask_channels(m)) for m in range(64)])
+
+
+def _parity(T, n_opt, cases):
     XO, UO, _, _ = windows(n_opt, T)
-    for pname, noise, measured in all_cases():
+    for pname, noise, measured in cases:
         L, Pm, Pp, status = _device(XO, UO, prior(pname, n_opt), noise, measured)
         assert L.shape == Pm.shape == Pp.shape == (n_opt, 6, 6, T) and not status.any()
         off = [c for c in range(6) if c not in measured]

@@ -11,7 +11,7 @@ import pytest
 
 from oracle import oracle as orc
 from test_gpu_covariance import MC_M, MC_SEED, MC_T, g4_jacobians, mc_members, offset_nominal, windows, z_scores  # noqa: F401
-from test_gpu_ensemble import DELTA_SCALE, SIGMA, _g4, _problem, deltas
+from test_gpu_ensemble import DELTA_SCALE, SIGMA, _g4, _problem, deltas, numpy_stats
 
 pytestmark = pytest.mark.gpu
 
@@ -25,9 +25,15 @@ SEED = 20261019
 REF_GAP = 4.2e-14
 TOL = 16 * REF_GAP
 SIZES_T = (3, 17, 33, 200)
+# The horizon edges, run for B = 65 alone: a block of F / c / L records is reloaded while b * 16 <= T - 1, so at T = 16 and
+# 32 sample T-1 is the last record of a block and the next block is never loaded, at T = 18 the second block holds one
+# stage, and T = 4 is the first horizon with a stage that is neither the first nor the last.
+EDGE_T = (4, 16, 18, 32)
+EDGE_B = 65
 GEOMETRY = {1: (1, 64), 64: (1, 64), 65: (1, 128), 130: (3, 64)}   # members -> (n_opt, members_per_opt)
+# case -> (disturbance, measurement noise: True = RHO, "zero" = a rho of six zeros, False = rho NULL; ehat0)
 CASES = {"plain": (False, False, False), "noise": (True, False, False), "noise_rho": (True, True, False),
-         "ehat0": (True, True, True)}
+         "ehat0": (True, True, True), "rho_only": (False, True, False), "rho_zero": (True, "zero", False)}
 
 
 def lqg_loop(mdl, xo, uo, KK, L, jac, x0, ehat0=None, dist=None, meas=None, dtype=np.float64):
@@ -115,7 +121,8 @@ def case_inputs(name, T, B, n_opt):
     """-> sigma, rho, ehat0 (n_opt,6) of a case (None where the case has none)"""
     noise, rho, e0 = CASES[name]
     rng = np.random.default_rng(17)
-    return (SIGMA if noise else None), (RHO if rho else None), (rng.normal(size=(n_opt, 6)) * DELTA_SCALE * 0.5 if e0 else None)
+    rho = np.zeros(6) if rho == "zero" else (RHO if rho else None)
+    return (SIGMA if noise else None), rho, (rng.normal(size=(n_opt, 6)) * DELTA_SCALE * 0.5 if e0 else None)
 
 
 def setup(T, B, nominal=None):
@@ -161,9 +168,10 @@ def host_draws(B, T, sigma, rho):
 def reference_gap(sizes_T=SIZES_T, sizes_B=tuple(GEOMETRY)):
     """The checker's own rounding: the largest scaled gap between lqg_loop in fp64 and with the estimator in np.longdouble
     over the cases of test_parity_with_the_checker and test_a_nominal_that_is_not_a_rollout, on the host's restatement of
-    the device's draws.  Needs no GPU."""
+    the device's draws, and over test_parity_at_the_horizon_edges.  Needs no GPU."""
     worst = 0.0
     runs = [(T, B, None) for T in sizes_T for B in sizes_B] + [(33, 65, offset_nominal(33))]
+    runs += [(T, EDGE_B, None) for T in EDGE_T]
     for T, B, nominal in runs:
         XO, UO, KK, L, jac, d, n_opt, mpo, mdl = setup(T, B, nominal)
         sel = selection(B)
@@ -178,10 +186,10 @@ def reference_gap(sizes_T=SIZES_T, sizes_B=tuple(GEOMETRY)):
     return worst
 
 
-def _run(XO, UO, KK, L, d, mpo, sigma=None, rho=None, e0=None, trajectories=True, **kw):
+def _run(XO, UO, KK, L, d, mpo, sigma=None, rho=None, e0=None, trajectories=True, weights=None, **kw):
     from aircraftoptimalcontrol_amd import batch
     g = g4_jacobians()[0]
-    bp = _problem(dict(g, xx_opt=XO[0]))
+    bp = _problem(dict(g, xx_opt=XO[0]), weights)
     return batch.track_ensemble(bp, XO, UO, delta=d, KK=KK, members_per_opt=mpo, sigma=sigma, seed=SEED, filter=L, rho=rho,
                                 ehat0=e0, trajectories=trajectories, **kw)
 
@@ -193,7 +201,8 @@ def _parity(T, B, nominal=None):
         sigma, rho, e0 = case_inputs(name, T, B, n_opt)
         r = _run(XO, UO, KK, L, d, mpo, sigma, rho, e0)
         assert r["xx_reg"].shape == (B, 6, T) and r["est_stats"].shape == (B, 12) and not r["status"].any()
-        assert (sigma is not None) == bool(r["dist"].any()) and (rho is not None) == bool(r["meas"].any())
+        draws = rho is not None and bool(np.any(rho))
+        assert (sigma is not None) == bool(r["dist"].any()) and draws == bool(r["meas"].any())
         want = checker(mdl, XO, UO, KK, L, jac, d, mpo, sel, e0, r["dist"] if sigma is not None else None,
                        r["meas"] if rho is not None else None)
         worst = 0.0
@@ -203,7 +212,7 @@ def _parity(T, B, nominal=None):
             worst = max(worst, scaled_gap(got, [v[i:i + 1] for v in want], XO[k], UO[k]))
         print("T = %d, B = %d, %s: scaled gap %.3g (bound %.3g)" % (T, B, name, worst, TOL))
         assert worst <= TOL, (T, B, name, worst)
-        if rho is not None:   # the measurement stream is the fourth-word-1 stream of the disturbance's generator
+        if draws:   # the measurement stream is the fourth-word-1 stream of the disturbance's generator
             from aircraftoptimalcontrol_amd import mpc
             for t in (0, T - 1):
                 assert np.max(np.abs(r["meas"][:, :, t] - mpc.noise_draws(SEED, t, 0, B, RHO, 1))) <= 1e-13 * RHO.max()
@@ -215,8 +224,183 @@ def _parity(T, B, nominal=None):
 def test_parity_with_the_checker(T, B):
     """Windows of g4 with filter_gains' L; T = 3 is the shortest horizon, 17 and 33 end one sample behind a block of 16
     records, 200 spans many; 1, 64, 65 and 130 members are a lone lane, a full tile, a tile and a lane, and three optima.  The
-    checker is fed the device's own dist and meas.  Cases: plain; noise; noise + rho; ehat0."""
+    checker is fed the device's own dist and meas.  Cases: plain; noise; noise + rho; ehat0; rho without disturbance (the
+    noise model carries the seed and a sigma of zeros: dist is all zero, meas is not); a rho of six zeros."""
     _parity(T, B)
+
+
+@pytest.mark.parametrize("T", EDGE_T)
+def test_parity_at_the_horizon_edges(T):
+    """The parity test at the horizons EDGE_T (see there) with 65 members: both sides of the estimator's block reload.
+    Measured on an MI355X: at most 8.2e-15 over the six cases (bound 6.7e-13)."""
+    _parity(T, EDGE_B)
+
+
+KEYS = ("xx_reg", "uu_reg", "xhat", "dist", "meas", "stats", "est_stats", "status")
+
+
+def shared_stats(r, XO, UO, grp, weights=None):
+    """What stats (B,16) must be for the trajectories a call returned: column 8 from batch.traj_cost on a problem whose
+    per-trajectory reference is (XO[grp], UO[grp]) with the weights of the call, the others NumPy's subtract / abs / max on
+    the fetched xx_reg, uu_reg (tests/test_gpu_ensemble.py numpy_stats)."""
+    from aircraftoptimalcontrol_amd import batch
+    g = g4_jacobians()[0]
+    Q, R, QT = weights if weights is not None else (g["QQt"], g["RRt"], g["QQT"])
+    cost = batch.traj_cost(batch.BatchProblem(Q, R, QT, XO[grp], UO[grp], float(g["dt"])), r["xx_reg"], r["uu_reg"])
+    return numpy_stats(r["xx_reg"], r["uu_reg"], XO[grp], UO[grp], cost)
+
+
+def test_shared_statistics_with_a_working_filter():
+    """130 members about three optima, T = 33, noise + rho + ehat0, with g4's diagonal weights and with dense ones: the
+    sixteen shared statistics are those of the true trajectories about the optimum — the maxima of |dx| and |du|, the final
+    dx and first_bad NumPy's on the fetched xx_reg, uu_reg, the cost the bits of aoc_traj_cost with ref = (x_opt, u_opt) —
+    although the loop feeds back an estimate that differs from dx.  The weights enter nothing but the cost: every other
+    output of the two runs is bit-identical.  The same holds without trajectories (stats, est_stats, status) and without
+    any noise (ehat0 alone), with both weights.  Launches the eight fp64-state estimator instances of k_track_ensemble:
+    WRITE x NOISE x DIAG."""
+    from test_gpu_dense import _tracking_weights
+    T, B = 33, 130
+    XO, UO, KK, L, jac, d, n_opt, mpo, mdl = setup(T, B)
+    sigma, rho, e0 = case_inputs("ehat0", T, B, n_opt)
+    grp = np.arange(B) // mpo
+    dense = _tracking_weights()
+    other = [c for c in range(16) if c != 8]
+    for sg, rh in ((sigma, rho), (None, None)):                       # NOISE = true, false
+        full = {}
+        for name, w in (("diag", None), ("dense", dense)):            # DIAG = true, false
+            r = full[name] = _run(XO, UO, KK, L, d, mpo, sg, rh, e0, weights=w)           # WRITE = true
+            assert not r["status"].any() and np.abs(r["xhat"] - r["xx_reg"]).max() > 1e-4
+            assert np.array_equal(r["stats"], shared_stats(r, XO, UO, grp, w)), (name, sg is not None)
+            so = _run(XO, UO, KK, L, d, mpo, sg, rh, e0, trajectories=False, weights=w)   # WRITE = false
+            assert "xx_reg" not in so and "xhat" not in so
+            for k in ("stats", "est_stats", "status"):
+                assert np.array_equal(so[k], r[k]), (name, sg is not None, k)
+        for k in KEYS:
+            if k != "stats":
+                assert np.array_equal(full["diag"][k], full["dense"][k]), (sg is not None, k)
+        assert np.array_equal(full["diag"]["stats"][:, other], full["dense"]["stats"][:, other])
+        assert (full["diag"]["stats"][:, 8] != full["dense"]["stats"][:, 8]).all()
+
+
+def test_float32_state_storage():
+    """f32=True with ehat0 and no noise (the only form the call takes with float32 storage), 130 members, T = 33, diagonal and
+    dense weights — the two float32-state estimator instances: every output has the bits of the fp64-storage call, x_reg
+    included, since without a disturbance every state from sample 1 on is a float32 value.  With sigma or rho the call is
+    refused with its reason."""
+    from aircraftoptimalcontrol_amd import batch
+    from test_gpu_dense import _tracking_weights
+    T, B = 33, 130
+    XO, UO, KK, L, jac, d, n_opt, mpo, mdl = setup(T, B)
+    _, _, e0 = case_inputs("ehat0", T, B, n_opt)
+    for w in (None, _tracking_weights()):
+        a = _run(XO, UO, KK, L, d, mpo, None, None, e0, weights=w)
+        b = _run(XO, UO, KK, L, d, mpo, None, None, e0, weights=w, f32=True)
+        assert np.array_equal(a["xx_reg"][:, :, 1:], a["xx_reg"][:, :, 1:].astype(np.float32)) and not a["status"].any()
+        for k in KEYS:
+            assert np.array_equal(a[k], b[k]), k
+    for sg, rh in ((SIGMA, None), (None, RHO), (SIGMA, RHO)):
+        with pytest.raises(batch.AocError, match="float32 state storage .* cannot hold disturbed states"):
+            _run(XO, UO, KK, L, d, mpo, sg, rh, e0, f32=True)
+
+
+OUT_GROUPS = ("xu", "xhat", "dist", "meas")
+
+
+def abi_call(XO, UO, KK, L, d, mpo, sigma, rho, e0, outputs):
+    """One aoc_track_ensemble_lqg call marshalled as batch.track_ensemble marshals it, except that only the output groups
+    named in `outputs` (of OUT_GROUPS; "xu" = x_reg and u_reg, which go together) are passed and the others are NULL ->
+    dict of the arrays that were passed (xx_reg, uu_reg, xhat, dist, meas: (B,.,T)), stats (B,16), est_stats (B,12),
+    status (B,)."""
+    import ctypes as C
+    import torch
+    from aircraftoptimalcontrol_amd import _lib, batch
+    bp = _problem(dict(g4_jacobians()[0], xx_opt=XO[0]))
+    dev, T, n_opt, B = bp.device, bp.T, XO.shape[0], d.shape[0]
+    grp = np.arange(B) // mpo
+    nominal = torch.from_numpy(batch.ensemble_nominal(XO, UO, KK)).to(dev)
+    filt = batch._filter_to_device(L, n_opt, T, dev)
+    x0t = batch.pack_vec(XO[grp, :, 0] + d, dev)
+    e0_d = None if e0 is None else batch._dev_f64(np.ascontiguousarray(e0), dev)
+    nz = rho_c = None
+    if sigma is not None or rho is not None:
+        sg = np.zeros(6) if sigma is None else np.asarray(sigma, dtype=np.float64)
+        nz = _lib.MpcNoise(SEED, 0, 0, (C.c_double * 6)(*sg.tolist()))
+    if rho is not None:
+        rho_c = (C.c_double * 6)(*np.asarray(rho, dtype=np.float64).tolist())
+    assert set(outputs) <= set(OUT_GROUPS)
+    tiled = lambda group, c: batch.alloc_tiled(B, T, c, dev) if group in outputs else None
+    buf = dict(xx_reg=tiled("xu", 6), uu_reg=tiled("xu", 2), xhat=tiled("xhat", 6), dist=tiled("dist", 6), meas=tiled("meas", 6))
+    nt = batch.ntiles(B)
+    stats = torch.empty((nt, _lib.AOC_ENS_NSTAT, batch.TILE), dtype=torch.float64, device=dev)
+    est_stats = torch.empty((nt, _lib.AOC_LQG_NSTAT, batch.TILE), dtype=torch.float64, device=dev)
+    status = torch.zeros(nt * batch.TILE, dtype=torch.int32, device=dev)
+    nbytes = int(_lib.lib().aoc_track_ensemble_lqg_scratch_bytes(n_opt, T))
+    scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    p, ptr = bp.c_problem(B), batch._ptr
+    _lib.check(_lib.lib().aoc_track_ensemble_lqg(C.byref(p), n_opt, mpo, ptr(nominal), ptr(filt), ptr(x0t), ptr(e0_d),
+                                                 C.byref(nz) if nz is not None else None, rho_c, ptr(buf["xx_reg"]),
+                                                 ptr(buf["uu_reg"]), ptr(buf["xhat"]), ptr(buf["dist"]), ptr(buf["meas"]),
+                                                 ptr(stats), ptr(est_stats), ptr(status), ptr(scratch), nbytes),
+               "aoc_track_ensemble_lqg")
+    out = {k: batch.unpack(v, B).cpu().numpy() for k, v in buf.items() if v is not None}
+    out.update(stats=batch.unpack_vec(stats, B).cpu().numpy(), est_stats=batch.unpack_vec(est_stats, B).cpu().numpy(),
+               status=status[:B].cpu().numpy())
+    return out
+
+
+def test_every_output_may_be_null_on_its_own():
+    """The C ABI lets (x_reg, u_reg), xhat_reg, dist_out and meas_out be NULL each on its own; the Python call passes all or
+    none.  65 members, T = 17, noise + rho + ehat0: with all of them the helper's call has the bits of batch.track_ensemble;
+    with xhat alone, meas alone, dist alone, x and u alone, all but x and u, and none, every array that was passed and
+    stats, est_stats, status have the bits of the call with all."""
+    T, B = 17, 65
+    XO, UO, KK, L, jac, d, n_opt, mpo, mdl = setup(T, B)
+    sigma, rho, e0 = case_inputs("ehat0", T, B, n_opt)
+    r = _run(XO, UO, KK, L, d, mpo, sigma, rho, e0)
+    full = abi_call(XO, UO, KK, L, d, mpo, sigma, rho, e0, OUT_GROUPS)
+    assert sorted(full) == sorted(KEYS)
+    for k in KEYS:
+        assert np.array_equal(full[k], r[k]), k
+    for outputs in (("xhat",), ("meas",), ("dist",), ("xu",), ("xhat", "meas", "dist"), ()):
+        got = abi_call(XO, UO, KK, L, d, mpo, sigma, rho, e0, outputs)
+        arrays = [k for grp_, ks in (("xu", ("xx_reg", "uu_reg")), ("xhat", ("xhat",)), ("dist", ("dist",)),
+                                     ("meas", ("meas",))) if grp_ in outputs for k in ks]
+        assert sorted(got) == sorted(arrays + ["stats", "est_stats", "status"]), outputs
+        for k in got:
+            assert np.array_equal(got[k], full[k]), (outputs, k)
+
+
+def test_a_rho_of_zeros_is_no_measurement_noise():
+    """rho = six zeros beside a disturbance: every output has the bits of the call with rho = NULL, and meas is +0.0
+    throughout, no sign bit set."""
+    T, B = 33, 130
+    XO, UO, KK, L, jac, d, n_opt, mpo, mdl = setup(T, B)
+    a = _run(XO, UO, KK, L, d, mpo, *case_inputs("noise", T, B, n_opt))
+    b = _run(XO, UO, KK, L, d, mpo, *case_inputs("rho_zero", T, B, n_opt))
+    for k in KEYS:
+        assert np.array_equal(a[k], b[k]), k
+    assert not b["meas"].any() and not np.signbit(b["meas"]).any() and b["dist"].any()
+
+
+def test_both_streams_follow_step0_and_first():
+    """step0 = 7, first = 192, 65 members, T = 17: meas[:, :, t] is the fourth-word-1 stream at step 7 + t of the members
+    192 .., dist[:, :, t] the fourth-word-0 stream there (1e-13 of the largest std, the gate of the draws elsewhere in this
+    file); the two streams differ in every draw."""
+    from aircraftoptimalcontrol_amd import mpc
+    T, B = 17, 65
+    XO, UO, KK, L, jac, d, n_opt, mpo, mdl = setup(T, B)
+    r = _run(XO, UO, KK, L, d, mpo, SIGMA, RHO, None, step0=7, first=192)
+    assert not r["status"].any()
+    for t in range(T):
+        assert np.max(np.abs(r["meas"][:, :, t] - mpc.noise_draws(SEED, 7 + t, 192, B, RHO, 1))) <= 1e-13 * RHO.max(), t
+    for t in range(T - 1):
+        assert np.max(np.abs(r["dist"][:, :, t] - mpc.noise_draws(SEED, 7 + t, 192, B, SIGMA))) <= 1e-13 * SIGMA.max(), t
+    assert not r["dist"][:, :, T - 1].any()
+    zm, zd = r["meas"][:, :, :T - 1] / RHO[None, :, None], r["dist"][:, :, :T - 1] / SIGMA[None, :, None]
+    assert (zm != zd).all()
+    # and they are not the draws of step0 = 0, first = 0
+    r0 = _run(XO, UO, KK, L, d, mpo, SIGMA, RHO, None)
+    assert (r0["meas"] != r["meas"]).all() and (r0["dist"][:, :, :T - 1] != r["dist"][:, :, :T - 1]).all()
 
 
 def test_a_nominal_that_is_not_a_rollout():

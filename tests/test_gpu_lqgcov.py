@@ -16,7 +16,8 @@ of du is the bound s_r = sum_j max_t |K_rj| (dX_j + dE_j), the largest du_r the 
 import numpy as np
 import pytest
 
-from test_gpu_covariance import (MC_M, MC_SEED, MC_T, TRI, g4_jacobians, mc_members, offset_nominal, start_moments, windows,
+from test_gpu_covariance import (EDGE_N, EDGE_T, G13_BOUND, MC_M, MC_SEED, MC_T, TRI, g4_jacobians, g13_gains, g13_gap,
+                                 g13_optima, g13_problem, g13_report, mc_members, offset_nominal, start_moments, windows,
                                  z_scores)
 from test_gpu_ensemble import DELTA_SCALE, SIGMA, _g4, _problem
 from test_gpu_filter import checked_optima, sequential_gains
@@ -168,8 +169,8 @@ def all_gaps(got, want, name, KK):
 
 def reference_gap(sizes_T=SIZES_T, sizes_n=SIZES_N):
     """The checker's own rounding: the largest gap between numpy_joint in fp64 and in np.longdouble over the cases of
-    test_parity_with_the_checker and test_a_nominal_that_is_not_a_rollout, on host_gains' L -> (gap, the case that sets it).
-    Needs no GPU."""
+    test_parity_with_the_checker, test_parity_at_the_horizon_edges (EDGE_T of tests/test_gpu_covariance.py, three optima)
+    and test_a_nominal_that_is_not_a_rollout, on host_gains' L -> (gap, the case that sets it).  Needs no GPU."""
     worst, which = 0.0, None
 
     def one(tag, name, jac, xo, KK, k):
@@ -182,8 +183,8 @@ def reference_gap(sizes_T=SIZES_T, sizes_n=SIZES_N):
         for part, v in g.items():
             if v > worst:
                 worst, which = v, tag + (name, part)
-    for T in sizes_T:
-        ks = sorted({k for n in sizes_n for k in checked_optima(n)})
+    for T in tuple(sizes_T) + EDGE_T:
+        ks = checked_optima(EDGE_N) if T in EDGE_T else sorted({k for n in sizes_n for k in checked_optima(n)})
         XO, _, KK, jac = windows(max(ks) + 1, T)
         for k in ks:
             for name in CASES:
@@ -283,6 +284,18 @@ def test_parity_with_the_checker(T, n_opt):
     the 16-sample prefetch, 65 optima are more wavefronts than one.  The cases of CASES: the Kalman gains of aoc_filter_gains
     with all channels, {0, 1, 4} and {0} measured, a detuned filter (the gains of 4 rho applied with rho, ehat0 != mean0 != 0,
     a full Sigma0), L = 0, without W, without rho.  The checker runs on the very L the device was handed."""
+    _parity(T, n_opt)
+
+
+@gpu
+@pytest.mark.parametrize("T", EDGE_T)
+def test_parity_at_the_horizon_edges(T):
+    """The parity test at the horizons EDGE_T of tests/test_gpu_covariance.py (both sides of the 16-sample prefetch's block
+    edge, a block of one stage, the first inner stage) with three optima."""
+    _parity(T, EDGE_N)
+
+
+def _parity(T, n_opt):
     XO, UO, KK, jac = windows(n_opt, T)
     for name in CASES:
         got, status, pred, L, (m0, e0, S0, sigma, rho) = _case_call(name, XO, UO, KK)
@@ -321,6 +334,43 @@ def test_a_nominal_that_is_not_a_rollout():
         assert np.abs(got[0, 1:, 0:6]).max() > 1e-6
         if name == "kalman":   # ehat0 = mean0: the error starts with mean 0 and neither c nor dx enters it
             assert not got[0, :, 6:12].any()
+
+
+@gpu
+def test_stage_records_at_wide_angles():
+    """Both k_cov_stage instances off the g4 fixture, read through aoc_track_covariance_lqg alone: three-sample optima on all
+    216 points of G13 (g13_optima of tests/test_gpu_covariance.py), filter = 0, mean0 = e_j, no Sigma0, no noise, no rho.
+    Setting (a), ehat0 = 0: the error starts at mu_0 = e_j and entries 6-11 of sample 1 are mu_1 = A[:, j], the record of
+    k_cov_stage<false>: against the golden fx per entry over |A_ij|, bound 1e-12 (the gate of aoc_step_batch on these
+    Jacobians), zero outside A's sparsity — and with the bits they have when the nominal carries the seeded K instead of
+    K = 0: a filter knows its input.  Setting (b), ehat0 = mean0 = e_j with the seeded K: mu = 0 and entries 0-5 of sample 1
+    are m_1 = F[:, j] of k_cov_stage<true>, against A + B K over |A_ij| + sum_r |B_ir K_rj|, the same bound.  status as in
+    tests/test_gpu_covariance.py.
+    Measured on an MI355X: (a) 3.92e-13; (b) 3.49e-13, both at entry (2, 2) of point 133."""
+    from test_gpu_parity import _record
+    K = g13_gains()
+    g, XO, UO, KK, A, B = g13_optima(K)
+    n = XO.shape[0]
+    bp = g13_problem(g)
+    L = np.zeros((n, 6, 6, 3))
+    want_status = np.where(XO[:, 2, 1] <= 0, ST_VNONPOS, 0)
+    Amu, Amu0, F = np.zeros((n, 6, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6, 6))
+    for j in range(6):
+        e = np.eye(6)[j]
+        a, st, _ = _predict(bp, XO, UO, KK, L, e, None, None, None, None)                      # (a), the seeded K
+        a0, st0, _ = _predict(bp, XO, UO, np.zeros_like(KK), L, e, None, None, None, None)     # (a), K = 0
+        b, stb, _ = _predict(bp, XO, UO, KK, L, e, e, None, None, None)                        # (b)
+        Amu[:, :, j], Amu0[:, :, j], F[:, :, j] = a[:, 1, 6:12], a0[:, 1, 6:12], b[:, 1, 0:6]
+        assert np.array_equal(a[:, 0, 6:12], np.broadcast_to(e, (n, 6))) and not b[:, :2, 6:12].any()
+        for s in (st, st0, stb):
+            assert np.array_equal(s, want_status), j
+    assert np.array_equal(Amu, Amu0)
+    gap_a, point_a, entry_a = g13_gap(Amu, A, B)
+    gap_b, point_b, entry_b = g13_gap(F, A, B, K)
+    rec = dict(points=n, A=g13_report("mu_1 = A through aoc_track_covariance_lqg", gap_a, point_a, entry_a, g),
+               F=g13_report("m_1 = A + B K through aoc_track_covariance_lqg", gap_b, point_b, entry_b, g))
+    _record("g13_lqgcov_stage.json", rec)
+    assert gap_a <= G13_BOUND and gap_b <= G13_BOUND, (gap_a, point_a, entry_a, gap_b, point_b, entry_b)
 
 
 @gpu
