@@ -17,6 +17,8 @@ AOC_TILE = 64
 AOC_ENS_NSTAT = 16   # statistics per member of aoc_track_ensemble
 AOC_ENV_NREC = 44    # doubles per (optimum, sample) record of aoc_track_ensemble_envelope
 AOC_HIST_NCH, AOC_HIST_NBIN = 8, 64   # channels (dx[0..5], du[0..1]) and bins per channel of aoc_track_ensemble_histogram
+AOC_SAT_NSTAT = 6    # cut statistics per member of aoc_track_ensemble_limited
+ENS_MODE_STATS, ENS_MODE_ENVELOPE, ENS_MODE_HISTOGRAM = 0, 1, 2   # `mode` of aoc_track_ensemble_limited
 AOC_COV_NREC = 32    # doubles per (optimum, sample) record of aoc_track_covariance
 AOC_LQG_NSTAT = 12   # estimation-error statistics per member of aoc_track_ensemble_lqg
 AOC_FILT_NREC = 42   # doubles per (optimum, sample) covariance record of aoc_filter_gains: upper triangles of P^- and P^+
@@ -69,6 +71,11 @@ class Params(C.Structure):
 class MpcNoise(C.Structure):
     """aoc_mpc_noise (include/aoc.h): the disturbance model aoc_mpc_step draws on the device."""
     _fields_ = [("seed", C.c_uint64), ("step", C.c_uint32), ("first", C.c_uint32), ("sigma", C.c_double * 6)]
+
+
+class ActuatorLimits(C.Structure):
+    """aoc_actuator_limits (include/aoc.h): range and slew rate of thrust and pitching moment; infinite = none."""
+    _fields_ = [("lo", C.c_double * 2), ("hi", C.c_double * 2), ("rate", C.c_double * 2)]
 
 
 class Tuning(C.Structure):
@@ -129,6 +136,8 @@ SYMBOLS = {
     "aoc_track_ensemble_envelope": (C.c_int, [_P, _I, _I] + [_P] * 10 + [_Z]),
     "aoc_ensemble_histogram_scratch_bytes": (_Z, [_I, _I, _I]),
     "aoc_track_ensemble_histogram": (C.c_int, [_P, _I, _I] + [_P] * 11 + [_Z]),
+    "aoc_ensemble_limited_scratch_bytes": (_Z, [_I] * 5),
+    "aoc_track_ensemble_limited": (C.c_int, [_P, _I, _I, _I] + [_P] * 15 + [_Z]),
     "aoc_track_covariance_scratch_bytes": (_Z, [_I, _I]),
     "aoc_track_covariance": (C.c_int, [_P, _I] + [_P] * 7 + [_Z]),
     "aoc_track_ensemble_lqg_scratch_bytes": (_Z, [_I, _I]),

@@ -986,6 +986,7 @@ ENV_NREC = _lib.AOC_ENV_NREC       # doubles per (optimum, sample) record of aoc
 HIST_NCH = _lib.AOC_HIST_NCH       # channels of aoc_track_ensemble_histogram: dx[0..5], du[0..1]
 HIST_NBIN = _lib.AOC_HIST_NBIN     # bins per (optimum, sample, channel)
 COV_NREC = _lib.AOC_COV_NREC       # doubles per (optimum, sample) record of aoc_track_covariance
+SAT_NSTAT = _lib.AOC_SAT_NSTAT     # cut statistics per member of aoc_track_ensemble_limited
 LQG_NSTAT = _lib.AOC_LQG_NSTAT     # estimation-error statistics per member of aoc_track_ensemble_lqg
 FILT_NREC = _lib.AOC_FILT_NREC     # doubles per (optimum, sample) covariance record of aoc_filter_gains
 LQGCOV_NREC = _lib.AOC_LQGCOV_NREC # doubles per (optimum, sample) record of aoc_track_covariance_lqg
@@ -1106,6 +1107,44 @@ def histogram_merge(a, b):
         raise ValueError("two integer arrays of counts (..., %d, %d) of one shape expected, got %s %s %s %s"
                          % (HIST_NCH, HIST_NBIN, a.shape, a.dtype, b.shape, b.dtype))
     return a.astype(np.int64) + b.astype(np.int64)
+
+
+def sat_count_merge(a, b):
+    """Cut counts (..., T, 2) of two disjoint sets of members of the same optimum under the SAME limits -> the counts of
+    their union: addition.  What joins calls cut by `first=`, shards and devices.  NumPy only, needs no GPU."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.ndim < 2 or a.shape[-1] != 2 or a.dtype.kind not in "iu" or b.dtype.kind not in "iu":
+        raise ValueError("two integer arrays of counts (..., T, 2) of one shape expected, got %s %s %s %s"
+                         % (a.shape, a.dtype, b.shape, b.dtype))
+    return a.astype(np.int64) + b.astype(np.int64)
+
+
+def frac_cut(sat):
+    """sat (M, 6) of some members -> (2,): per channel the share of them that is cut at least once (sat[:, 0:2] > 0; a
+    member whose demand is NaN throughout is never cut).  NaN for no members.  NumPy only, needs no GPU."""
+    sat = np.asarray(sat, dtype=np.float64)
+    if sat.ndim != 2 or sat.shape[1] != SAT_NSTAT:
+        raise ValueError("cut statistics (M, %d) expected, got %s" % (SAT_NSTAT, sat.shape))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (sat[:, 0:2] > 0).sum(axis=0) / np.float64(sat.shape[0])
+
+
+def actuator_limits(u_min=None, u_max=None, u_rate=None):
+    """The three keywords of track_ensemble -> lo, hi, rate (2,) fp64 with None (the keyword or a component) = unbounded;
+    ValueError for a shape other than (2,), a NaN, lo > hi or rate <= 0 — what aoc_track_ensemble_limited refuses."""
+    def two(v, default, name):
+        if v is None:
+            return np.full(2, default)
+        a = np.array([default if c is None else c for c in v] if np.ndim(v) == 1 else v, dtype=np.float64)
+        if a.shape != (2,) or np.isnan(a).any():
+            raise ValueError("%s must be (2,) = (thrust, pitching moment) without NaN, got %r" % (name, v))
+        return a
+    lo, hi, rate = two(u_min, -np.inf, "u_min"), two(u_max, np.inf, "u_max"), two(u_rate, np.inf, "u_rate")
+    if (lo > hi).any():
+        raise ValueError("u_min = %s exceeds u_max = %s" % (lo, hi))
+    if (rate <= 0).any():
+        raise ValueError("u_rate = %s must be positive (None or inf: no rate limit)" % (rate,))
+    return lo, hi, rate
 
 
 def histogram_quantiles(hist, bins, q):
@@ -1478,7 +1517,7 @@ def _ens_summary(torch, v):
 def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, sigma=None, seed=20260405, first=0,
                    step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True, envelope=False,
                    quantiles=None, bins=None, predict=False, mean0=None, Sigma0=None, predict_k=6.0, rho=None, filter=None,
-                   ehat0=None, measured=None, predict_joint=False):
+                   ehat0=None, measured=None, predict_joint=False, u_min=None, u_max=None, u_rate=None):
     """Closed-loop tracking ensemble about shared optima (aoc_track_ensemble): the loop of lqr_tracking.py:279-281 for B
     members, u_t = u_opt_t + K_t (x_t - x_opt_t), x_{t+1} = step(x_t, u_t) + d_t, reduced to per-member statistics on
     the device; the optimum and its gains are stored once per optimum, not once per member.
@@ -1530,8 +1569,24 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     `predicted_joint`, per optimum what linear theory gives for THIS loop — lqg_covariance_moments' dict, the joint moments
     of dx and of the estimation error e — and `predicted_joint_status` (n_opt,).  mean0 / Sigma0 = None: the population
     moments of each group's own initial deviations, as for predict=True (with filter="device", Sigma0 is the filter's
-    prior as well).  ValueError without filter=."""
+    prior as well).  ValueError without filter=.
+    u_min, u_max, u_rate (each (2,) = thrust, pitching moment; None or an infinite component: unbounded; u_rate in input
+    units per second) (aoc_track_ensemble_limited): the demand v_t = u_opt_t + K_t dx_t is cut to [u_min, u_max] and, from
+    sample 1 on, to within u_rate * dt of the input before (include/aoc.h) — and the cut input is what the plant and every
+    output above see; envelope=, quantiles=, trajectories= and f32= work as before, on this loop.  With none of the three
+    the calls and the result are what they were.  Adds sat (B,6) = per channel the number of cut samples, the first cut
+    sample (T if none) and max_t |v - u|; sat_count, per optimum (T,2) int32 = the members cut at each sample among those
+    still in the domain (sat_count_merge joins calls cut by `first=`); `limits` = dict(u_min, u_max, u_rate); and
+    summary[k]["frac_cut"] (2,) = the share of members cut at least once.  predict=True and bins="predicted" stay allowed,
+    but describe the UNLIMITED linear loop.  filter= together with a limit raises ValueError: the estimator's prediction
+    F = A + B K is wrong once the input is cut."""
     lqg = filter is not None
+    limited = u_min is not None or u_max is not None or u_rate is not None
+    if limited and lqg:
+        raise ValueError("filter= (the estimator in the loop) does not combine with u_min= / u_max= / u_rate=: its "
+                         "prediction F = A + B K is wrong once the input is cut")
+    if limited:
+        lim_lo, lim_hi, lim_rate = actuator_limits(u_min, u_max, u_rate)
     if predict_joint and not lqg:
         raise ValueError("predict_joint=True goes with filter= (the prediction of the LQG loop); predict=True is the "
                          "prediction of the loop that feeds back the true state")
@@ -1583,6 +1638,22 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
         nz = _lib.MpcNoise(int(seed), int(step0), int(first), (C.c_double * 6)(*np.asarray(sigma, dtype=np.float64).tolist()))
     p = problem.c_problem(B, x_out_f32=int(bool(f32)))
     nzp = C.byref(nz) if nz is not None else None
+    if limited:
+        lim = _lib.ActuatorLimits((C.c_double * 2)(*lim_lo.tolist()), (C.c_double * 2)(*lim_hi.tolist()),
+                                  (C.c_double * 2)(*lim_rate.tolist()))
+        sat = torch.empty((nt, SAT_NSTAT, TILE), dtype=torch.float64, device=dev)
+        sat_count = torch.empty((n_opt, T, 2), dtype=torch.int32, device=dev)
+
+        def limited_call(mode, out, st_, sts_, first_call, bins_d=None, env_d=None, hist_d=None):
+            """One aoc_track_ensemble_limited call; sat and sat_count are those of the first call over the members"""
+            sat_d = sat if first_call else torch.empty_like(sat)
+            cnt_d = sat_count if first_call else None
+            nbytes = int(lib().aoc_ensemble_limited_scratch_bytes(mode, B, T, mpo, int(first_call)))
+            scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+            check(lib().aoc_track_ensemble_limited(C.byref(p), mode, n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp, C.byref(lim),
+                                                   _ptr(bins_d), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(st_),
+                                                   _ptr(sts_), _ptr(sat_d), _ptr(cnt_d), _ptr(env_d), _ptr(hist_d),
+                                                   _ptr(scratch) if nbytes else None, nbytes), "aoc_track_ensemble_limited")
     hist = quantiles is not None
     bins_predicted = isinstance(bins, str)
     if bins_predicted:
@@ -1610,7 +1681,10 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
             envelope = True
     elif bins is not None:
         raise ValueError("bins= goes with quantiles=")
-    if envelope:
+    if envelope and limited:
+        env = torch.empty((n_opt, T, ENV_NREC), dtype=torch.float64, device=dev)
+        limited_call(_lib.ENS_MODE_ENVELOPE, (xr, ur, ds), stats, status, True, env_d=env)
+    elif envelope:
         env = torch.empty((n_opt, T, ENV_NREC), dtype=torch.float64, device=dev)
         nbytes = int(lib().aoc_ensemble_envelope_scratch_bytes(B, T, mpo))
         scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
@@ -1627,16 +1701,19 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
             bins = histogram_bins(env.cpu().numpy())
         bins_d = torch.from_numpy(np.ascontiguousarray(bins)).to(dev)
         hist_d = torch.empty((n_opt, T, HIST_NCH, HIST_NBIN), dtype=torch.int32, device=dev)
-        nbytes = int(lib().aoc_ensemble_histogram_scratch_bytes(B, T, mpo))
-        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
         first_call = not envelope
         h_stats, h_status = (stats, status) if first_call else (torch.empty_like(stats), torch.zeros_like(status))
         h_out = (xr, ur, ds) if first_call else (None, None, None)
-        check(lib().aoc_track_ensemble_histogram(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp, _ptr(bins_d),
-                                                 _ptr(h_out[0]), _ptr(h_out[1]), _ptr(h_out[2]), _ptr(h_stats), _ptr(h_status),
-                                                 _ptr(hist_d), _ptr(scratch) if nbytes else None, nbytes),
-              "aoc_track_ensemble_histogram")
-        del scratch
+        if limited:
+            limited_call(_lib.ENS_MODE_HISTOGRAM, h_out, h_stats, h_status, first_call, bins_d=bins_d, hist_d=hist_d)
+        else:
+            nbytes = int(lib().aoc_ensemble_histogram_scratch_bytes(B, T, mpo))
+            scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+            check(lib().aoc_track_ensemble_histogram(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp, _ptr(bins_d),
+                                                     _ptr(h_out[0]), _ptr(h_out[1]), _ptr(h_out[2]), _ptr(h_stats),
+                                                     _ptr(h_status), _ptr(hist_d), _ptr(scratch) if nbytes else None, nbytes),
+                  "aoc_track_ensemble_histogram")
+            del scratch
     if lqg:
         if device_gains:
             filt_d, _, filt_status = _filter_gains_device(problem, nominal, n_opt, Sigma0, sigma, rho, mask, False)
@@ -1673,6 +1750,8 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
                 jS0 = np.stack([np.cov(dx0[group == k].T, bias=True).reshape(6, 6) for k in range(n_opt)])
                 jS0 = 0.5 * (jS0 + jS0.transpose(0, 2, 1))
             joint_raw, joint_status = _predict_covariance_lqg(problem, nominal, filt_d, n_opt, jm0, ehat0, jS0, sigma, rho)
+    elif not envelope and not hist and limited:
+        limited_call(_lib.ENS_MODE_STATS, (xr, ur, ds), stats, status, True)
     elif not envelope and not hist:
         check(lib().aoc_track_ensemble(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(x0t), nzp,
                                        _ptr(xr), _ptr(ur), _ptr(ds), _ptr(stats), _ptr(status)), "aoc_track_ensemble")
@@ -1687,6 +1766,12 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     s = sv.cpu().numpy()
     out = dict(max_dx=s[:, 0:6], max_du=s[:, 6:8], cost=s[:, 8], final_dx=s[:, 9:15], first_bad=s[:, 15].astype(np.int64),
                status=status[:B].cpu().numpy(), stats=s, members_per_opt=mpo, group=group, summary=summary)
+    if limited:
+        sa = unpack_vec(sat, B).cpu().numpy()
+        for g, sm in enumerate(summary):
+            sm["frac_cut"] = frac_cut(sa[g * mpo:min((g + 1) * mpo, B)])
+        out.update(sat=sa, sat_count=list(sat_count.cpu().numpy()),
+                   limits=dict(u_min=lim_lo, u_max=lim_hi, u_rate=lim_rate))
     if lqg:
         es = unpack_vec(est_stats, B).cpu().numpy()
         out.update(est_stats=es, max_e=es[:, 0:6], sum_e2=es[:, 6:12])

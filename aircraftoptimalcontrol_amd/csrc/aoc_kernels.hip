@@ -542,6 +542,23 @@ int aoc_track_ensemble_histogram(const aoc_problem* p, int32_t n_opt, int32_t me
                                      noise, x_reg, u_reg, dist_out, stats, status, nullptr, bins, hist, scratch, scratch_bytes);
 }
 
+size_t aoc_ensemble_limited_scratch_bytes(int32_t mode, int32_t B, int32_t T, int32_t members_per_opt, int32_t with_sat_count) {
+    return aoc64::ensemble_limited_scratch_bytes(mode, B, T, members_per_opt, with_sat_count);
+}
+
+int aoc_track_ensemble_limited(const aoc_problem* p, int32_t mode, int32_t n_opt, int32_t members_per_opt, const double* nominal,
+                               const double* x0_reg, const aoc_mpc_noise* noise, const aoc_actuator_limits* limits,
+                               const double* bins, void* x_reg, double* u_reg, double* dist_out, double* stats, int32_t* status,
+                               double* sat, int32_t* sat_count, double* envelope, int32_t* hist, void* scratch,
+                               size_t scratch_bytes) {
+    static_assert(aoc64::LIM_NSTAT == AOC_SAT_NSTAT && sizeof(aoc_actuator_limits) == 48, "cut statistics and limits of the header");
+    static_assert(aoc64::ENS_PLAIN == AOC_ENS_MODE_STATS && aoc64::ENS_ENVELOPE == AOC_ENS_MODE_ENVELOPE &&
+                      aoc64::ENS_HISTOGRAM == AOC_ENS_MODE_HISTOGRAM, "modes of the launch function and of the header");
+    return aoc64::api_track_ensemble("aoc_track_ensemble_limited", mode, p, n_opt, members_per_opt, nominal, x0_reg, noise, x_reg,
+                                     u_reg, dist_out, stats, status, envelope, bins, hist, scratch, scratch_bytes, true, limits,
+                                     sat, sat_count);
+}
+
 size_t aoc_track_covariance_scratch_bytes(int32_t n_opt, int32_t T) {
     return aoc64::track_covariance_scratch_bytes(n_opt, T);
 }

@@ -133,6 +133,32 @@ struct EnsEst<true> {
     real* est_stats;       // [tile][EST_NSTAT][64]
 };
 
+// ---- actuator limits and rate limits in the loop (aoc_track_ensemble_limited) ---------------------------------------------
+// The LIM instances of k_track_ensemble cut the demand v_t = u_opt_t + K_t dx_t to what an actuator delivers: with the range
+// [lo, hi] and the slew s = rate * dt per sample (the product formed once on the host), channel r = 0 thrust, 1 moment,
+//     a = lo, b = hi at t = 0;   a = (uprev - s > lo) ? uprev - s : lo,   b = (uprev + s < hi) ? uprev + s : hi at t >= 1,
+//     u = v < a ? a : (v > b ? b : v),   uprev = u
+// — selections only (a NaN demand fails both comparisons and stays NaN; fmin / fmax would drop it), so with infinite limits
+// every output has the bits of the instance without limits.  uprev starts as NaN: both comparisons of a and b fail, which IS
+// the rule for t = 0 (there is no u_-1), without a branch on t.  u is what the plant, the cost, every statistic, the envelope
+// and the histogram see.  A sample is CUT in channel r when v < a || v > b.
+// sat[tile][LIM_NSTAT][64]: 0-1 number of cut samples, 2-3 first cut sample (T if none), 4-5 max_t |v - u| (a NaN sticks).
+// cnt (may be NULL): per sample and channel the number of members of the tile that count on the envelope's terms and are
+// cut — a ballot and a population count, kept by lane 2 (t % ENS_BLK) + r and written as the tile's partial
+// cnt[tile][t][2] once per block of stages (128 contiguous bytes); k_sat_fold adds the tiles of an optimum.
+constexpr int LIM_NSTAT = 6;    // AOC_SAT_NSTAT
+static_assert(2 * ENS_BLK <= TILE, "one lane per sample and channel of a block of stages");
+
+// what the LIM instances take beside the arguments of every instance (nothing otherwise)
+template <bool LIM>
+struct EnsLim {};
+template <>
+struct EnsLim<true> {
+    real lo[2], hi[2], s[2];   // s = rate * dt
+    real* sat;                 // [tile][LIM_NSTAT][64]
+    int* cnt;                  // [tile][T][2] or NULL
+};
+
 // max over |v| with a NaN that sticks (fmax would drop it): for non-negative doubles the IEEE order is the order of
 // the bit patterns as unsigned integers, and every NaN lies above +inf there
 __device__ __forceinline__ void ens_absmax(unsigned long long& m, double v) {
@@ -150,16 +176,20 @@ __device__ __forceinline__ bool ens_finite6(const real x[6]) {
 // ENV: also the per-tile envelope records part[tile][t][ENV_NREC] (above); every other output keeps its bits.
 // HIST: also the per-tile byte counts part[tile][t][HIST_NCH][HIST_NBIN] under `bins` (above); never together with ENV.
 // EST: the input is fed back from the estimate of `est` (above) instead of the true deviation; never with ENV or HIST.
-template <bool WRITE, bool NOISE, typename XO, bool DIAG, bool ENV = false, bool HIST = false, bool EST = false>
+// LIM: the input is cut to the limits of `lim` (above), with sat and the cut counts; never with EST.
+template <bool WRITE, bool NOISE, typename XO, bool DIAG, bool ENV = false, bool HIST = false, bool EST = false,
+          bool LIM = false>
 __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_per_opt, const real* __restrict__ nominal,
                                                          const real* __restrict__ x0, MpcNoise nz, XO* __restrict__ x_reg,
                                                          real* __restrict__ u_reg, real* __restrict__ dist_out,
                                                          real* __restrict__ stats, int* __restrict__ status,
                                                          real* __restrict__ part = nullptr,
-                                                         const real* __restrict__ bins = nullptr, EnsEst<EST> est = {}) {
+                                                         const real* __restrict__ bins = nullptr, EnsEst<EST> est = {},
+                                                         EnsLim<LIM> lim = {}) {
 #pragma clang fp contract(off)
     static_assert(!(ENV && HIST), "the bins come from an envelope call: the two are never one instance");
     static_assert(!(EST && (ENV || HIST)), "the estimator instances reduce nothing over the members");
+    static_assert(!(EST && LIM), "the estimator predicts with F = A + B K: not the loop whose input is cut");
     __shared__ __attribute__((aligned(16))) real sh[2][ENS_BLK * ENS_REC];
     __shared__ __attribute__((aligned(16))) real ev[ENV ? ENV_S * ENV_ROWS * ENV_LD : 2];
     __shared__ __attribute__((aligned(16))) real hb[HIST ? 2 * ENS_BLK * HIST_REC : 2];
@@ -390,6 +420,20 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
     unsigned long long mx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     real JJ = R(0.0);
     int flags = 0, first_bad = T;
+    // limits: the input of the sample before, the three cut statistics per channel, this lane's count of the block
+    real up[2] = {(real)__builtin_nan(""), (real)__builtin_nan("")};
+    unsigned long long msat[2] = {0, 0};
+    int ncut[2] = {0, 0}, fcut[2] = {T, T}, cacc = 0;
+    // the six limits in VGPRs, like the weights above: the SGPRs are full, and uniform values they do not hold are parked in
+    // VGPR lanes and fetched with v_readlane in every stage
+    real llo[2], lhi[2], ls[2];
+    if constexpr (LIM) {
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            llo[r] = lim.lo[r]; lhi[r] = lim.hi[r]; ls[r] = lim.s[r];
+            vpin(llo[r]); vpin(lhi[r]); vpin(ls[r]);
+        }
+    }
 #pragma unroll
     for (int c = 0; c < 6; c++) {
         xs[c] = x0[((size_t)tile * 6 + c) * TILE + lane];
@@ -424,6 +468,27 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
         if (vbad) flags |= AOC_ST_VNONPOS;
         if (nonfin) flags |= AOC_ST_NAN;
         if ((vbad || nonfin) && t < first_bad) first_bad = t;
+        if constexpr (LIM) {
+            const real v[2] = {u0, u1};
+            real u[2];
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const real dn = up[r] - ls[r], hn = up[r] + ls[r];
+                const real a = dn > llo[r] ? dn : llo[r], bb = hn < lhi[r] ? hn : lhi[r];
+                const bool cut = v[r] < a || v[r] > bb;
+                u[r] = v[r] < a ? a : (v[r] > bb ? bb : v[r]);
+                up[r] = u[r];
+                ncut[r] += cut ? 1 : 0;
+                fcut[r] = cut && t < fcut[r] ? t : fcut[r];
+                ens_absmax(msat[r], v[r] - u[r]);
+                // counted whether cnt is asked for or not (a compare's mask, two scalar and two vector instructions): a branch
+                // here would cut the stage into blocks
+                const int n_cut = __popcll(__ballot(cut && in_B && first_bad > t));
+                cacc = lane == 2 * i + r ? n_cut : cacc;
+            }
+            u0 = u[0];
+            u1 = u[1];
+        }
 #pragma unroll
         for (int c = 0; c < 6; c++) ens_absmax(mx[c], d[c]);
         ens_absmax(mx[6], u0 - cur[6]);
@@ -468,6 +533,12 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
 #pragma unroll
         for (int c = 0; c < 6; c++) xs[c] = xn[c];
       }
+      if constexpr (LIM) {
+          if (lim.cnt) {   // the samples t0 .. t0 + n - 1 <= T-2 of the tile, two counts each
+              if (lane < 2 * n) lim.cnt[((size_t)tile * T + t0) * 2 + lane] = cacc;
+              cacc = 0;
+          }
+      }
       stash(b + 1);
     }
     // sample T-1: deviation, terminal cost, the last look at the domain (no input, no gain: only x_opt of the record is used)
@@ -507,6 +578,15 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
     for (int c = 0; c < 6; c++) so[(9 + c) * TILE] = dT[c];
     so[15 * TILE] = (real)first_bad;
     if (status && flags) status[tile * TILE + lane] |= flags;
+    if constexpr (LIM) {
+        real* __restrict__ sa = lim.sat + (size_t)tile * LIM_NSTAT * TILE + lane;
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            sa[r * TILE] = (real)ncut[r];
+            sa[(2 + r) * TILE] = (real)fcut[r];
+            sa[(4 + r) * TILE] = (real)__longlong_as_double((long long)msat[r]);
+        }
+    }
     if constexpr (EST) {
         real* __restrict__ eo = est.est_stats + (size_t)tile * EST_NSTAT * TILE + lane;
 #pragma unroll
@@ -578,6 +658,33 @@ __global__ __launch_bounds__(ENV_FOLD_THREADS) void k_histogram_fold(int n_opt, 
     ((int4*)hist)[idx] = make_int4(acc[0], acc[1], acc[2], acc[3]);
 }
 
+// sat_count[opt][t][r] (int32) from cnt[tile][t][r]: the tiles of an optimum added up, one thread per number (sixteen loads
+// in flight).  Integers: any order gives the same.  Sample T-1 has no input: 0, and no tile wrote it.
+template <typename = void>
+__global__ __launch_bounds__(ENV_FOLD_THREADS) void k_sat_fold(int n_opt, int T, int ntiles, int tiles_per_opt,
+                                                               const int* __restrict__ cnt, int* __restrict__ sat_count) {
+    const size_t per_opt = (size_t)T * 2, idx = (size_t)blockIdx.x * ENV_FOLD_THREADS + threadIdx.x;
+    if (idx >= (size_t)n_opt * per_opt) return;
+    const int opt = (int)(idx / per_opt);
+    const size_t in_opt = idx - (size_t)opt * per_opt;
+    const int first = opt * tiles_per_opt, last = first + tiles_per_opt < ntiles ? first + tiles_per_opt : ntiles;
+    int acc = 0;
+    if (in_opt < per_opt - 2) {
+        const int* __restrict__ src = cnt + (size_t)first * per_opt + in_opt;
+        int i = first;
+        for (; i + 16 <= last; i += 16) {
+            int v[16];
+#pragma unroll
+            for (int j = 0; j < 16; j++) v[j] = src[(size_t)j * per_opt];
+#pragma unroll
+            for (int j = 0; j < 16; j++) acc += v[j];
+            src += 16 * per_opt;
+        }
+        for (; i < last; i++, src += per_opt) acc += *src;
+    }
+    sat_count[idx] = acc;
+}
+
 #ifndef AOC_KERNELS_ONLY
 // aoc_ensemble_envelope_scratch_bytes: part[ntiles][T][ENV_NREC]; 0 for a geometry the call refuses anyway
 static size_t ensemble_envelope_scratch_bytes(int32_t B, int32_t T, int32_t members_per_opt) {
@@ -592,6 +699,15 @@ static size_t ensemble_histogram_scratch_bytes(int32_t B, int32_t T, int32_t mem
 }
 
 enum { ENS_PLAIN = 0, ENS_ENVELOPE = 1, ENS_HISTOGRAM = 2 };
+
+// aoc_ensemble_limited_scratch_bytes: what the mode's own call takes, rounded up to 16 bytes, then the cut counts'
+// cnt[ntiles][T][2] int32 if sat_count is asked for; 0 for a mode or a geometry the call refuses anyway
+static size_t ensemble_limited_scratch_bytes(int32_t mode, int32_t B, int32_t T, int32_t members_per_opt, int32_t with_sat_count) {
+    if (mode < ENS_PLAIN || mode > ENS_HISTOGRAM || B < 1 || T < 1 || members_per_opt < TILE || members_per_opt % TILE) return 0;
+    const size_t own = mode == ENS_ENVELOPE ? ensemble_envelope_scratch_bytes(B, T, members_per_opt)
+                                            : (mode == ENS_HISTOGRAM ? ensemble_histogram_scratch_bytes(B, T, members_per_opt) : 0);
+    return ((own + 15) & ~(size_t)15) + (with_sat_count ? (size_t)((B + TILE - 1) / TILE) * (size_t)T * 2 * sizeof(int) : 0);
+}
 
 // The refusals every ensemble call shares (aoc_track_ensemble and what builds on it, lqg.inc included), in the order they are
 // reported; `missing` names a further argument of the caller's that is NULL and must not be (or is nullptr).
@@ -633,6 +749,8 @@ static MpcNoise ens_noise(const aoc_mpc_noise* noise) {
     return nz;
 }
 
+// Limits (aoc_track_ensemble_limited): `limited` with limits, sat (neither NULL) and sat_count (may be NULL); scratch is then
+// laid out as ensemble_limited_scratch_bytes says and its size query is named in the reasons.
 // Body of aoc_track_ensemble, (mode ENS_ENVELOPE: with envelope, scratch, scratch_bytes) of aoc_track_ensemble_envelope and
 // (mode ENS_HISTOGRAM: with bins, hist, scratch, scratch_bytes) of aoc_track_ensemble_histogram, fn the name
 // of the entry point for the reasons.  A template only so that the kernels it names are instantiated where it is called
@@ -641,29 +759,64 @@ template <typename = void>
 static int api_track_ensemble(const char* fn, int mode, const aoc_problem* p, int32_t n_opt, int32_t members_per_opt,
                               const real* nominal, const real* x0_reg, const aoc_mpc_noise* noise, void* x_reg, real* u_reg,
                               real* dist_out, real* stats, int32_t* status, real* envelope, const real* bins, int32_t* hist,
-                              void* scratch, size_t scratch_bytes) {
+                              void* scratch, size_t scratch_bytes, bool limited = false,
+                              const aoc_actuator_limits* limits = nullptr, real* sat = nullptr, int32_t* sat_count = nullptr) {
+    if (mode < ENS_PLAIN || mode > ENS_HISTOGRAM)
+        return einval("%s: mode = %d (0 statistics, 1 envelope, 2 histogram)", fn, mode);
     const bool env = mode == ENS_ENVELOPE, hst = mode == ENS_HISTOGRAM;
-    const char* missing = env && !envelope ? "envelope" : (hst && !bins ? "bins" : (hst && !hist ? "hist" : nullptr));
+    const char* missing = limited && !limits ? "limits" : (limited && !sat ? "sat" : nullptr);
+    if (!missing) missing = env && !envelope ? "envelope" : (hst && !bins ? "bins" : (hst && !hist ? "hist" : nullptr));
     if (int rc = ens_check_args(fn, p, n_opt, members_per_opt, nominal, x0_reg, noise, x_reg, u_reg, stats, missing)) return rc;
-    if (env) {
-        const size_t need = ensemble_envelope_scratch_bytes(p->B, p->T, members_per_opt);
-        if (!scratch) return einval("%s: scratch is NULL (need %zu bytes, aoc_ensemble_envelope_scratch_bytes)", fn, need);
-        if (scratch_bytes < need)
-            return einval("%s: scratch_bytes = %zu, need %zu (aoc_ensemble_envelope_scratch_bytes)", fn, scratch_bytes, need);
+    if (limited) {
+        for (int r = 0; r < 2; r++) {
+            if (limits->lo[r] != limits->lo[r] || limits->hi[r] != limits->hi[r] || limits->rate[r] != limits->rate[r])
+                return einval("%s: limits has a NaN in channel %d (lo = %g, hi = %g, rate = %g; infinite values mean none)", fn, r,
+                              limits->lo[r], limits->hi[r], limits->rate[r]);
+            if (limits->lo[r] > limits->hi[r])
+                return einval("%s: limits.lo[%d] = %g > limits.hi[%d] = %g", fn, r, limits->lo[r], r, limits->hi[r]);
+            if (limits->rate[r] <= 0)
+                return einval("%s: limits.rate[%d] = %g (need rate > 0; +inf means none)", fn, r, limits->rate[r]);
+        }
     }
-    if (hst) {
-        const size_t need = ensemble_histogram_scratch_bytes(p->B, p->T, members_per_opt);
-        if (!scratch) return einval("%s: scratch is NULL (need %zu bytes, aoc_ensemble_histogram_scratch_bytes)", fn, need);
-        if (scratch_bytes < need)
-            return einval("%s: scratch_bytes = %zu, need %zu (aoc_ensemble_histogram_scratch_bytes)", fn, scratch_bytes, need);
-        if ((uintptr_t)scratch % 16 || (uintptr_t)hist % 16)
-            return einval("%s: scratch and hist must be 16-byte aligned", fn);
+    const char* query = limited ? "aoc_ensemble_limited_scratch_bytes"
+                                : (env ? "aoc_ensemble_envelope_scratch_bytes" : "aoc_ensemble_histogram_scratch_bytes");
+    const size_t need = limited ? ensemble_limited_scratch_bytes(mode, p->B, p->T, members_per_opt, sat_count != nullptr)
+                                : (env ? ensemble_envelope_scratch_bytes(p->B, p->T, members_per_opt)
+                                       : (hst ? ensemble_histogram_scratch_bytes(p->B, p->T, members_per_opt) : 0));
+    if (env || hst || need) {
+        if (!scratch) return einval("%s: scratch is NULL (need %zu bytes, %s)", fn, need, query);
+        if (scratch_bytes < need) return einval("%s: scratch_bytes = %zu, need %zu (%s)", fn, scratch_bytes, need, query);
     }
+    if (hst && ((uintptr_t)scratch % 16 || (uintptr_t)hist % 16))
+        return einval("%s: scratch and hist must be 16-byte aligned", fn);
+    if (limited && sat_count && (uintptr_t)scratch % 4) return einval("%s: scratch must be 4-byte aligned", fn);
     KConst k = make_const(p->model, p->QQt, p->RRt, p->QQT, p->B, p->T);
     const MpcNoise nz = ens_noise(noise);
     hipStream_t st = (hipStream_t)p->stream;
     const int tpo = members_per_opt / TILE;
     const bool write = x_reg || dist_out;
+    EnsLim<true> lm;
+    int* cnt = nullptr;
+    if (limited) {
+        for (int r = 0; r < 2; r++) {
+            lm.lo[r] = limits->lo[r];
+            lm.hi[r] = limits->hi[r];
+            lm.s[r] = limits->rate[r] * p->model.dt;   // the slew per sample, formed once, here
+        }
+        if (sat_count)
+            cnt = (int*)((char*)scratch + ensemble_limited_scratch_bytes(mode, p->B, p->T, members_per_opt, 0));
+        lm.sat = sat;
+        lm.cnt = cnt;
+    }
+    // the cut counts of the tiles folded into sat_count, behind the kernels of the mode
+    auto finish = [&]() -> int {
+        if (int rc = check_launch(fn)) return rc;
+        if (!cnt) return AOC_OK;
+        const size_t total = (size_t)n_opt * p->T * 2;
+        hipLaunchKernelGGL(k_sat_fold<>, dim3((unsigned)((total + ENV_FOLD_THREADS - 1) / ENV_FOLD_THREADS)),
+                           dim3(ENV_FOLD_THREADS), 0, st, n_opt, p->T, k.ntiles, tpo, (const int*)cnt, sat_count);
+        return check_launch(fn);
+    };
 #define AOC_ENS_LAUNCH(W, N, XO, D)                                                                                     \
     hipLaunchKernelGGL((k_track_ensemble<W, N, XO, D>), dim3(k.ntiles), dim3(TILE), 0, st, k, tpo, nominal, x0_reg, nz, \
                        (XO*)x_reg, u_reg, dist_out, stats, status)
@@ -673,6 +826,17 @@ static int api_track_ensemble(const char* fn, int mode, const aoc_problem* p, in
 #define AOC_HIST_LAUNCH(W, N, XO, D)                                                                                            \
     hipLaunchKernelGGL((k_track_ensemble<W, N, XO, D, false, true>), dim3(k.ntiles), dim3(TILE), 0, st, k, tpo, nominal, x0_reg, \
                        nz, (XO*)x_reg, u_reg, dist_out, stats, status, (real*)scratch, bins)
+#define AOC_LIM_LAUNCH(W, N, XO, D)                                                                                     \
+    hipLaunchKernelGGL((k_track_ensemble<W, N, XO, D, false, false, false, true>), dim3(k.ntiles), dim3(TILE), 0, st, k, tpo, \
+                       nominal, x0_reg, nz, (XO*)x_reg, u_reg, dist_out, stats, status, (real*)nullptr, (const real*)nullptr, \
+                       EnsEst<false>{}, lm)
+#define AOC_LIM_ENV_LAUNCH(W, N, XO, D)                                                                                 \
+    hipLaunchKernelGGL((k_track_ensemble<W, N, XO, D, true, false, false, true>), dim3(k.ntiles), dim3(TILE), 0, st, k, tpo, \
+                       nominal, x0_reg, nz, (XO*)x_reg, u_reg, dist_out, stats, status, (real*)scratch, (const real*)nullptr, \
+                       EnsEst<false>{}, lm)
+#define AOC_LIM_HIST_LAUNCH(W, N, XO, D)                                                                                \
+    hipLaunchKernelGGL((k_track_ensemble<W, N, XO, D, false, true, false, true>), dim3(k.ntiles), dim3(TILE), 0, st, k, tpo, \
+                       nominal, x0_reg, nz, (XO*)x_reg, u_reg, dist_out, stats, status, (real*)scratch, bins, EnsEst<false>{}, lm)
 #define AOC_ENS_DISPATCH(LAUNCH)                                                                                        \
     do {                                                                                                                \
         if (p->x_out_f32 && x_reg) /* (never with noise, see above) */                                                  \
@@ -681,27 +845,39 @@ static int api_track_ensemble(const char* fn, int mode, const aoc_problem* p, in
             AOC_DISPATCH_BOOL(write, W, AOC_DISPATCH_BOOL(nz.on, N, AOC_DISPATCH_BOOL(k.diag, D, LAUNCH(W, N, double, D)))); \
     } while (0)
     if (mode == ENS_PLAIN) {
-        AOC_ENS_DISPATCH(AOC_ENS_LAUNCH);
-        return check_launch(fn);
+        if (limited)
+            AOC_ENS_DISPATCH(AOC_LIM_LAUNCH);
+        else
+            AOC_ENS_DISPATCH(AOC_ENS_LAUNCH);
+        return finish();
     }
     if (hst) {
-        AOC_ENS_DISPATCH(AOC_HIST_LAUNCH);
+        if (limited)
+            AOC_ENS_DISPATCH(AOC_LIM_HIST_LAUNCH);
+        else
+            AOC_ENS_DISPATCH(AOC_HIST_LAUNCH);
         if (int rc = check_launch(fn)) return rc;
         const size_t total = (size_t)n_opt * p->T * HIST_DW;
         hipLaunchKernelGGL(k_histogram_fold<>, dim3((unsigned)((total + ENV_FOLD_THREADS - 1) / ENV_FOLD_THREADS)),
                            dim3(ENV_FOLD_THREADS), 0, st, n_opt, p->T, k.ntiles, tpo, (const unsigned*)scratch, hist);
-        return check_launch(fn);
+        return finish();
     }
-    AOC_ENS_DISPATCH(AOC_ENV_LAUNCH);
+    if (limited)
+        AOC_ENS_DISPATCH(AOC_LIM_ENV_LAUNCH);
+    else
+        AOC_ENS_DISPATCH(AOC_ENV_LAUNCH);
     if (int rc = check_launch(fn)) return rc;
     const size_t total = (size_t)n_opt * p->T * ENV_NREC;
     hipLaunchKernelGGL(k_envelope_fold<>, dim3((unsigned)((total + ENV_FOLD_THREADS - 1) / ENV_FOLD_THREADS)),
                        dim3(ENV_FOLD_THREADS), 0, st, n_opt, p->T, k.ntiles, tpo, (const real*)scratch, envelope);
 #undef AOC_ENS_DISPATCH
+#undef AOC_LIM_HIST_LAUNCH
+#undef AOC_LIM_ENV_LAUNCH
+#undef AOC_LIM_LAUNCH
 #undef AOC_HIST_LAUNCH
 #undef AOC_ENV_LAUNCH
 #undef AOC_ENS_LAUNCH
-    return check_launch(fn);
+    return finish();
 }
 #endif  // AOC_KERNELS_ONLY
 

@@ -9,6 +9,7 @@ JSON line.
                                              [--envelope FILE.npz] [--quantiles FILE.npz [--q 0.05 0.5 0.95]]
                                              [--predict FILE.npz] [--rho r0 r1 r2 r3 r4 r5 [--device-gains] [--measured c ...]
                                                                    [--predict-joint FILE.npz]]
+                                             [--u-min a b] [--u-max a b] [--u-rate a b]
 
 --envelope FILE.npz: also reduce over the members at every sample on the device (the tube around the optimum) and save
 n (T,), min_dx / max_dx (6,T), min_du / max_du (2,T), mean_dx (6,T), cov_dx (6,6,T), raw (T,44); the JSON line then
@@ -34,6 +35,11 @@ cov_e, cov_dx_e, cov_xhat (6,6,T), mean_du (2,T), cov_du (2,2,T), raw (T,96), st
 "predict_joint": the file, and "predicted_rms_dx" / "predicted_rms_estimation_error" beside the sampled "rms_dx" /
 "rms_estimation_error": per channel the root of the mean over the samples of variance + mean^2.  The members' trajectories
 are then kept on the device to sample rms_dx (26 doubles per member and sample).
+--u-min a b, --u-max a b, --u-rate a b (thrust, pitching moment; any of the three, inf = unbounded): the demand of every
+member is cut to the range and, from sample 1 on, to within u-rate * dt of the input before (aoc_track_ensemble_limited);
+every other output is then that of the limited loop (--predict stays the prediction of the UNLIMITED linear loop).  The JSON
+line then carries "limits": the three pairs (null = unbounded), and "frac_cut": per channel the share of members cut at
+least once.  Not together with --rho.
 """
 import argparse
 import json
@@ -62,10 +68,17 @@ def main():
     ap.add_argument("--measured", type=int, nargs="+", default=None, help="with --device-gains: the channels the filter measures")
     ap.add_argument("--predict-joint", default=None, metavar="FILE.npz",
                     help="with --rho: save the joint linear prediction of dx and of the estimation error")
+    ap.add_argument("--u-min", type=float, nargs=2, default=None, metavar=("THRUST", "MOMENT"), help="lower limit of the inputs")
+    ap.add_argument("--u-max", type=float, nargs=2, default=None, metavar=("THRUST", "MOMENT"), help="upper limit of the inputs")
+    ap.add_argument("--u-rate", type=float, nargs=2, default=None, metavar=("THRUST", "MOMENT"),
+                    help="largest change of the inputs per second")
     ap.add_argument("--q", type=float, nargs="+", default=[0.05, 0.5, 0.95], help="quantile levels of --quantiles")
     a = ap.parse_args()
     if a.rho is not None and (a.envelope or a.quantiles or a.predict):
         ap.error("--rho does not combine with --envelope, --quantiles or --predict")
+    limits = {k: v for k, v in (("u_min", a.u_min), ("u_max", a.u_max), ("u_rate", a.u_rate)) if v is not None}
+    if limits and a.rho is not None:
+        ap.error("--u-min / --u-max / --u-rate do not combine with --rho (the estimator predicts with the uncut input)")
     if a.predict_joint is not None and a.rho is None:
         ap.error("--predict-joint goes with --rho (the prediction of the loop with the estimator; --predict is the other one)")
     xx_opt = np.load(os.path.join(a.data, "xx_star.npy"))
@@ -86,11 +99,14 @@ def main():
     else:
         r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, envelope=a.envelope is not None,
                                  quantiles=a.q if a.quantiles is not None else None, predict=a.predict is not None,
-                                 mean0=np.zeros(6), Sigma0=np.diag(np.asarray(a.delta) ** 2))
+                                 mean0=np.zeros(6), Sigma0=np.diag(np.asarray(a.delta) ** 2), **limits)
     sm = r["summary"][0]
     tolist = lambda d: {k: np.asarray(v).tolist() for k, v in d.items()}
     line = dict(members=a.members, T=T, sigma=a.sigma, left_the_domain=sm["n_bad"],
                 max_dx=tolist(sm["max_dx"]), final_dx=tolist(sm["final_dx"]), cost=tolist(sm["cost"]))
+    if limits:
+        finite = lambda v: [float(c) if np.isfinite(c) else None for c in v]
+        line.update(limits={k: finite(v) for k, v in r["limits"].items()}, frac_cut=sm["frac_cut"].tolist())
     if a.rho is not None:
         line.update(rho=list(a.rho), rms_estimation_error=np.sqrt(r["sum_e2"].mean(axis=0) / T).tolist())
     if a.predict_joint is not None:

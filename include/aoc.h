@@ -70,7 +70,9 @@ extern "C" {
  *      (still 5, an addition: aoc_filter_gains, aoc_filter_gains_scratch_bytes — no struct, argument list or size query of
  *      an existing entry changed)
  *      (still 5, an addition: aoc_track_covariance_lqg, aoc_track_covariance_lqg_scratch_bytes — no struct, argument list or
- *      size query of an existing entry changed) */
+ *      size query of an existing entry changed)
+ *      (still 5, an addition: aoc_track_ensemble_limited, aoc_ensemble_limited_scratch_bytes, struct aoc_actuator_limits — no
+ *      struct, argument list or size query of an existing entry changed) */
 #define AOC_ABI_VERSION 5
 
 #define AOC_TILE 64
@@ -602,6 +604,54 @@ int aoc_track_ensemble_histogram(const aoc_problem *prob, int32_t n_opt, int32_t
                                  const double *x0_reg, const aoc_mpc_noise *noise, const double *bins, void *x_reg,
                                  double *u_reg, double *dist_out, double *stats, int32_t *status, int32_t *hist,
                                  void *scratch, size_t scratch_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The same ensemble with ACTUATOR LIMITS AND RATE LIMITS in the loop: the demand of lqr_tracking.py:280 is cut to what the
+ * actuators deliver before the plant sees it.  With s[r] = limits->rate[r] * prob->model.dt (one fp64 product, formed on the
+ * host), channel r = 0 thrust, r = 1 pitching moment, sample t = 0 .. T-2 of every member does
+ *     v[r] = u_opt_t[r] + sum_c K_t[r][c] dx_t[c]                              the demand, summed as in aoc_track_ensemble
+ *     a[r] = lo[r], b[r] = hi[r]                                               at t = 0 (there is no u_-1: no rate limit)
+ *     a[r] = (uprev[r] - s[r] > lo[r]) ? uprev[r] - s[r] : lo[r]               at t >= 1, one rounding each
+ *     b[r] = (uprev[r] + s[r] < hi[r]) ? uprev[r] + s[r] : hi[r]
+ *     u[r] = v[r] < a[r] ? a[r] : (v[r] > b[r] ? b[r] : v[r])                  a NaN demand stays NaN
+ *     uprev[r] = u[r],   x_{t+1} = Dynamics.step(x_t, u) + d_t
+ * u is what the plant, the cost, statistics 6-7, u_reg, the envelope and the histogram see.  The limits are selections, not
+ * arithmetic: with lo = -inf, hi = +inf, rate = +inf every output shared with the calls without limits has their bits.  A
+ * sample is CUT in channel r when v[r] < a[r] || v[r] > b[r] (never for a NaN demand).
+ * mode: AOC_ENS_MODE_STATS (the outputs of aoc_track_ensemble), AOC_ENS_MODE_ENVELOPE (also `envelope`, as
+ *   aoc_track_ensemble_envelope) or AOC_ENS_MODE_HISTOGRAM (also `hist` under `bins`, as aoc_track_ensemble_histogram);
+ *   arguments of the other modes are not read.  Every argument shared with those calls means what it means there and is
+ *   checked as there, in the same order.
+ * limits: HOST pointer like noise, not NULL.  Infinite values are legal and mean "none"; rate is in input units per second.
+ * sat: DEVICE, fp64, [ntiles][AOC_SAT_NSTAT][64] per member, not NULL:
+ *   0-1   number of cut samples of channel r, t <= T-2        2-3   first cut sample; T if none
+ *   4-5   max over t of |v[r] - u[r]| (a NaN sticks)
+ * sat_count: DEVICE, int32, [n_opt][T][2], may be NULL (then not computed): the number of members of the optimum that are cut
+ *   in channel r at sample t, among those that COUNT on the envelope's terms (b < B and t < stats[15] of b).  Sample T-1 is 0.
+ *   Exact integers, the same on every run and with or without trajectories; counts of disjoint member sets merge by addition.
+ *   The other outputs do not change with or without it.
+ * scratch: DEVICE, caller-owned, at least aoc_ensemble_limited_scratch_bytes(mode, B, T, members_per_opt, sat_count != NULL)
+ *   bytes: what the mode's own call takes (rounded up to 16) and 8 * T * ceil(B / 64) for the tiles' cut counts.  0 (scratch
+ *   may be NULL) for AOC_ENS_MODE_STATS without sat_count.  Alignment as the mode's own call asks.
+ * AOC_EINVAL with the reason, before anything touches a device: the refusals of the mode's own call; mode not one of the
+ * three; limits NULL; sat NULL; a NaN in lo, hi or rate; lo[r] > hi[r]; rate[r] <= 0.
+ * The ensemble kernel (one more instance per mode; the arithmetic of a stage is shared), the mode's fold, and with sat_count
+ * a fold of the tiles' counts.  No atomics.
+ * Not covered: limits in the loop of aoc_track_ensemble_lqg (its estimator predicts with F = A + B K, which is wrong once the
+ * input is cut), limits that vary with time or optimum, a rate limit at t = 0.
+ * --------------------------------------------------------------------------------------------- */
+#define AOC_SAT_NSTAT 6
+enum { AOC_ENS_MODE_STATS = 0, AOC_ENS_MODE_ENVELOPE = 1, AOC_ENS_MODE_HISTOGRAM = 2 };
+typedef struct aoc_actuator_limits {
+    double lo[2], hi[2];   /* range of thrust, pitching moment */
+    double rate[2];        /* largest change per second (times model.dt: per sample) */
+} aoc_actuator_limits;
+size_t aoc_ensemble_limited_scratch_bytes(int32_t mode, int32_t B, int32_t T, int32_t members_per_opt, int32_t with_sat_count);
+int aoc_track_ensemble_limited(const aoc_problem *prob, int32_t mode, int32_t n_opt, int32_t members_per_opt,
+                               const double *nominal, const double *x0_reg, const aoc_mpc_noise *noise,
+                               const aoc_actuator_limits *limits, const double *bins, void *x_reg, double *u_reg,
+                               double *dist_out, double *stats, int32_t *status, double *sat, int32_t *sat_count,
+                               double *envelope, int32_t *hist, void *scratch, size_t scratch_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * What LINEAR theory predicts for the same closed loop: the mean and covariance of dx = x - x_opt under the Lyapunov recursion

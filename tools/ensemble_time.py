@@ -2,7 +2,7 @@
 """Closed-loop tracking ensemble about ONE optimum: aoc_track_ensemble against the replicated path it replaces.
 
     python tools/ensemble_time.py [--members 65536 262144] [--T 1000] [--seconds 0.5] [--repeats 3] [--out FILE]
-                                  [--envelope] [--histogram] [--predict] [--lqg] [--filter]
+                                  [--envelope] [--histogram] [--predict] [--lqg] [--filter] [--limits]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/ensemble_time.py --trace --members N
     python tools/ensemble_time.py --kernel-times DIR                 (kernel times: a traced run of its own, then its summary)
 
@@ -57,6 +57,12 @@ and reports J_n / P_n and J_n / G_n against the chains of --predict and --filter
 The optimum is the g4 fixture's (T = 1000; --T cuts it), the members are seeded perturbations of its first sample.
 Profiler off: HIP events around at least --seconds of back-to-back launches per variant, after a warm-up of every variant;
 the variants take turns inside each of --repeats rounds, so that a drift of the machine hits all of them.  One JSON line:
+--limits adds the loop with actuator limits (aoc_track_ensemble_limited), statistics only, no disturbance:
+  M_fixed    under the magnitude limits (-140, -260) .. (360, 430) and the rate limits (8200, 69000) per second of
+             tests/test_limits_abi.py, no sat_count
+  M_inf      under infinite limits (the outputs of B_stats, bit for bit), no sat_count
+  M_count    as M_fixed, with sat_count (the tiles' counts and their fold)
+and reports each over B_stats of the same run.
 per size and variant the ms per call of every round, B/A, member-stages per second, and — from --valu, the vector
 instructions of one stage on the executed path of the ISA (tools/one_kernel.sh, tools/isa_loops.py) — the share of the fp64
 vector-issue roof (1024 SIMDs, one instruction per 4 cycles at 2.4 GHz): this kernel's bound is issue, not HBM.
@@ -78,7 +84,7 @@ DELTA_SCALE = np.array([0.3, 0.3, 0.5, 0.05, 0.1, 0.05])
 SIGMA = np.array([1e-3, 1e-3, 1e-2, 1e-4, 1e-3, 1e-4])
 
 
-def setup(B, T, g, envelope=False, histogram=False, lqg=False):
+def setup(B, T, g, envelope=False, histogram=False, lqg=False, limits=False):
     """Device buffers and the launch closures for B members."""
     import torch
     from aircraftoptimalcontrol_amd import _lib, batch
@@ -132,6 +138,24 @@ def setup(B, T, g, envelope=False, histogram=False, lqg=False):
                   "aoc_track_ensemble_lqg")
 
         runs.update(L_plain=run_L, L_noise=lambda: run_L(noise=True))
+    if limits:
+        inf = float("inf")
+        two = lambda a, b: (C.c_double * 2)(a, b)
+        fixed = _lib.ActuatorLimits(two(-140.0, -260.0), two(360.0, 430.0), two(8200.0, 69000.0))
+        none = _lib.ActuatorLimits(two(-inf, -inf), two(inf, inf), two(inf, inf))
+        sat = torch.empty((nt, batch.SAT_NSTAT, TILE), dtype=torch.float64, device=dev)
+        sat_count = torch.empty((1, T, 2), dtype=torch.int32, device=dev)
+        mbytes = int(lib().aoc_ensemble_limited_scratch_bytes(_lib.ENS_MODE_STATS, B, T, nt * TILE, 1))
+        mscratch = torch.empty(mbytes // 8, dtype=torch.float64, device=dev)
+
+        def run_M(lim, count=False):
+            check(lib().aoc_track_ensemble_limited(C.byref(pB), _lib.ENS_MODE_STATS, 1, nt * TILE, _ptr(nominal), _ptr(x0t), None,
+                                                   C.byref(lim), None, None, None, None, _ptr(stats), _ptr(status), _ptr(sat),
+                                                   _ptr(sat_count) if count else None, None, None,
+                                                   _ptr(mscratch) if count else None, mbytes if count else 0),
+                  "aoc_track_ensemble_limited")
+
+        runs.update(M_fixed=lambda: run_M(fixed), M_inf=lambda: run_M(none), M_count=lambda: run_M(fixed, True))
     if not envelope and not histogram:
         return runs
     # E: trajectories in fp64 + a torch reduction on the tiled arrays [tile][t][c][lane]
@@ -501,7 +525,7 @@ def kernel_times(d):
     out = collections.OrderedDict()
     for name, t0, t1, grid in sorted(rows, key=lambda r: r[1]):
         name = name.split("(")[0].replace("void ", "").replace("aoc64::", "")
-        if name.startswith(("k_track_", "k_envelope_", "k_histogram_", "k_cov_", "k_filter_", "k_lqgcov_")):
+        if name.startswith(("k_track_", "k_envelope_", "k_histogram_", "k_cov_", "k_filter_", "k_lqgcov_", "k_sat_")):
             out.setdefault("%s grid=%s" % (name, grid), []).append(round((t1 - t0) / 1e6, 4))
     for k, v in out.items():
         print(json.dumps(dict(kernel=k, ms=v, median=float(np.median(v)), spread_rel=round((max(v) - min(v)) / float(np.median(v)), 4))))
@@ -522,6 +546,7 @@ def main():
     ap.add_argument("--lqg", action="store_true", help="also time aoc_track_ensemble_lqg, statistics only, with and without draws")
     ap.add_argument("--filter", action="store_true", help="also time aoc_filter_gains for 1, 64 and 1024 optima")
     ap.add_argument("--joint", action="store_true", help="also time aoc_track_covariance_lqg for 1, 64 and 1024 optima")
+    ap.add_argument("--limits", action="store_true", help="also time aoc_track_ensemble_limited, statistics only")
     ap.add_argument("--hist-valu", type=int, default=0, help="vector instructions per stage of the histogram kernel (from the ISA)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -535,10 +560,10 @@ def main():
     for B in a.members:
         rec = dict(members=B)
         try:
-            runs = setup(B, a.T, g, a.envelope, a.histogram or a.predict, a.lqg)
+            runs = setup(B, a.T, g, a.envelope, a.histogram or a.predict, a.lqg, a.limits)
             if a.predict:
                 if not a.histogram:       # the yardsticks of the prediction only, not the torch routes to the histogram
-                    runs = {k: f for k, f in runs.items() if k in ("A", "B_stats", "B_noise", "B_env", "H", "L_plain", "L_noise")}
+                    runs = {k: f for k, f in runs.items() if k in ("A", "B_stats", "B_noise", "B_env", "H", "L_plain", "L_noise", "M_fixed", "M_inf", "M_count")}
                 runs.update(setup_predict(a.T, g))
             if a.filter:
                 if not a.predict:
@@ -583,6 +608,12 @@ def main():
                                   B_noise_ms=med["B_noise"], L_noise_over_B_noise=round(med["L_noise"] / med["B_noise"], 4),
                                   L_plain_over_B_stats=round(med["L_plain"] / med["B_stats"], 4),
                                   spread_rel={k: sp(k) for k in ("L_plain", "L_noise", "B_stats", "B_noise")})
+            if a.limits:
+                sp = lambda k: round((max(ms[k]) - min(ms[k])) / med[k], 4)
+                ks = ("M_fixed", "M_inf", "M_count")
+                rec["limits"] = dict(B_stats_ms=med["B_stats"], **{k + "_ms": med[k] for k in ks},
+                                     **{k + "_over_B_stats": round(med[k] / med["B_stats"], 4) for k in ks},
+                                     spread_rel={k: sp(k) for k in ks + ("B_stats",)})
             if a.filter:
                 sp = lambda k: round((max(ms[k]) - min(ms[k])) / med[k], 4)
                 ns = (1, 64, 1024)
