@@ -21,6 +21,7 @@ AOC_SAT_NSTAT = 6    # cut statistics per member of aoc_track_ensemble_limited
 ENS_MODE_STATS, ENS_MODE_ENVELOPE, ENS_MODE_HISTOGRAM = 0, 1, 2   # `mode` of aoc_track_ensemble_limited
 AOC_COV_NREC = 32    # doubles per (optimum, sample) record of aoc_track_covariance
 AOC_LQG_NSTAT = 12   # estimation-error statistics per member of aoc_track_ensemble_lqg
+EST_INPUT_DEMANDED, EST_INPUT_APPLIED = 0, 1   # `est_input` of aoc_track_ensemble_lqg_limited
 AOC_FILT_NREC = 42   # doubles per (optimum, sample) covariance record of aoc_filter_gains: upper triangles of P^- and P^+
 AOC_LQGCOV_NREC = 96 # doubles per (optimum, sample) record of aoc_track_covariance_lqg
 AOC_ABI_VERSION = 5   # include/aoc.h: the revision this binding (struct layouts, argument lists) is written against
@@ -142,6 +143,8 @@ SYMBOLS = {
     "aoc_track_covariance": (C.c_int, [_P, _I] + [_P] * 7 + [_Z]),
     "aoc_track_ensemble_lqg_scratch_bytes": (_Z, [_I, _I]),
     "aoc_track_ensemble_lqg": (C.c_int, [_P, _I, _I] + [_P] * 15 + [_Z]),
+    "aoc_track_ensemble_lqg_limited_scratch_bytes": (_Z, [_I] * 5),
+    "aoc_track_ensemble_lqg_limited": (C.c_int, [_P, _I, _I] + [_P] * 7 + [_I] + [_P] * 11 + [_Z]),
     "aoc_filter_gains_scratch_bytes": (_Z, [_I, _I]),
     "aoc_filter_gains": (C.c_int, [_P, _I] + [_P] * 4 + [_I] + [_P] * 4 + [_Z]),
     "aoc_track_covariance_lqg_scratch_bytes": (_Z, [_I, _I]),

@@ -1517,7 +1517,7 @@ def _ens_summary(torch, v):
 def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, sigma=None, seed=20260405, first=0,
                    step0=0, members_per_opt=None, trajectories=False, f32=False, to_host=True, envelope=False,
                    quantiles=None, bins=None, predict=False, mean0=None, Sigma0=None, predict_k=6.0, rho=None, filter=None,
-                   ehat0=None, measured=None, predict_joint=False, u_min=None, u_max=None, u_rate=None):
+                   ehat0=None, measured=None, predict_joint=False, u_min=None, u_max=None, u_rate=None, est_input=None):
     """Closed-loop tracking ensemble about shared optima (aoc_track_ensemble): the loop of lqr_tracking.py:279-281 for B
     members, u_t = u_opt_t + K_t (x_t - x_opt_t), x_{t+1} = step(x_t, u_t) + d_t, reduced to per-member statistics on
     the device; the optimum and its gains are stored once per optimum, not once per member.
@@ -1578,13 +1578,27 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
     sample (T if none) and max_t |v - u|; sat_count, per optimum (T,2) int32 = the members cut at each sample among those
     still in the domain (sat_count_merge joins calls cut by `first=`); `limits` = dict(u_min, u_max, u_rate); and
     summary[k]["frac_cut"] (2,) = the share of members cut at least once.  predict=True and bins="predicted" stay allowed,
-    but describe the UNLIMITED linear loop.  filter= together with a limit raises ValueError: the estimator's prediction
-    F = A + B K is wrong once the input is cut."""
+    but describe the UNLIMITED linear loop.
+    filter= together with a limit and est_input="applied" | "demanded" (aoc_track_ensemble_lqg_limited): the demand
+    v_t = u_opt_t + K_t e^+_t of the estimator's loop is cut in the same way, and est_input says what the estimator's
+    prediction is told — "applied": the cut input, e^-_{t+1} = F_t e^+_t + c_t + B_t (u_t - v_t) where the sample is cut, which
+    restores the separation of the linear loop; "demanded": the estimator of filter= as it is, F = A + B K, which a cut
+    misleads.  Works with filter="device", rho=, ehat0=, trajectories= and f32=, not with envelope= or quantiles= (as for
+    filter=).  The result holds the outputs of filter= and sat, sat_count, limits and summary[k]["frac_cut"] as above, and
+    `est_input` as given.  predict_joint=True stays allowed but describes the loop WITHOUT limits.  filter= together with a
+    limit and no est_input= raises ValueError (the choice is the caller's), so does est_input= without both a filter and a
+    limit, or a name other than the two."""
     lqg = filter is not None
     limited = u_min is not None or u_max is not None or u_rate is not None
-    if limited and lqg:
-        raise ValueError("filter= (the estimator in the loop) does not combine with u_min= / u_max= / u_rate=: its "
-                         "prediction F = A + B K is wrong once the input is cut")
+    if limited and lqg and est_input is None:
+        raise ValueError("filter= (the estimator in the loop) does not combine with u_min= / u_max= / u_rate= unless est_input= "
+                         "says what its prediction is told: \"applied\" (the cut input) or \"demanded\" (F = A + B K as it "
+                         "is, which is wrong once the input is cut)")
+    if est_input is not None:
+        if not (limited and lqg):
+            raise ValueError("est_input= goes with filter= and a limit (u_min= / u_max= / u_rate=)")
+        if est_input not in ("applied", "demanded"):
+            raise ValueError('est_input=%r: the names are "applied" and "demanded"' % (est_input,))
     if limited:
         lim_lo, lim_hi, lim_rate = actuator_limits(u_min, u_max, u_rate)
     if predict_joint and not lqg:
@@ -1736,11 +1750,20 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
         xh = ms = None
         if trajectories:
             xh, ms = alloc_tiled(B, T, 6, dev), alloc_tiled(B, T, 6, dev)
-        nbytes = int(lib().aoc_track_ensemble_lqg_scratch_bytes(n_opt, T))
-        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
-        check(lib().aoc_track_ensemble_lqg(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(filt_d), _ptr(x0t), _ptr(e0_d), nzp, rho_c,
-                                           _ptr(xr), _ptr(ur), _ptr(xh), _ptr(ds), _ptr(ms), _ptr(stats), _ptr(est_stats),
-                                           _ptr(status), _ptr(scratch), nbytes), "aoc_track_ensemble_lqg")
+        if limited:
+            nbytes = int(lib().aoc_track_ensemble_lqg_limited_scratch_bytes(B, n_opt, T, mpo, 1))
+            scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+            told = _lib.EST_INPUT_APPLIED if est_input == "applied" else _lib.EST_INPUT_DEMANDED
+            check(lib().aoc_track_ensemble_lqg_limited(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(filt_d), _ptr(x0t), _ptr(e0_d),
+                                                       nzp, rho_c, C.byref(lim), told, _ptr(xr), _ptr(ur), _ptr(xh), _ptr(ds),
+                                                       _ptr(ms), _ptr(stats), _ptr(est_stats), _ptr(sat), _ptr(sat_count),
+                                                       _ptr(status), _ptr(scratch), nbytes), "aoc_track_ensemble_lqg_limited")
+        else:
+            nbytes = int(lib().aoc_track_ensemble_lqg_scratch_bytes(n_opt, T))
+            scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+            check(lib().aoc_track_ensemble_lqg(C.byref(p), n_opt, mpo, _ptr(nominal), _ptr(filt_d), _ptr(x0t), _ptr(e0_d), nzp,
+                                               rho_c, _ptr(xr), _ptr(ur), _ptr(xh), _ptr(ds), _ptr(ms), _ptr(stats),
+                                               _ptr(est_stats), _ptr(status), _ptr(scratch), nbytes), "aoc_track_ensemble_lqg")
         del scratch
         if predict_joint:
             dx0 = x0 - xo[group, :, 0]
@@ -1772,6 +1795,8 @@ def track_ensemble(problem, xx_opt, uu_opt, x0_reg=None, delta=None, KK=None, si
             sm["frac_cut"] = frac_cut(sa[g * mpo:min((g + 1) * mpo, B)])
         out.update(sat=sa, sat_count=list(sat_count.cpu().numpy()),
                    limits=dict(u_min=lim_lo, u_max=lim_hi, u_rate=lim_rate))
+        if lqg:
+            out["est_input"] = est_input
     if lqg:
         es = unpack_vec(est_stats, B).cpu().numpy()
         out.update(est_stats=es, max_e=es[:, 0:6], sum_e2=es[:, 6:12])

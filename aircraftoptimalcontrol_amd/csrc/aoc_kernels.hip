@@ -579,8 +579,25 @@ int aoc_track_ensemble_lqg(const aoc_problem* p, int32_t n_opt, int32_t members_
                            const double* rho, void* x_reg, double* u_reg, double* xhat_reg, double* dist_out, double* meas_out,
                            double* stats, double* est_stats, int32_t* status, void* scratch, size_t scratch_bytes) {
     static_assert(aoc64::EST_NSTAT == AOC_LQG_NSTAT, "estimation statistics of the kernel and of the header");
-    return aoc64::api_track_ensemble_lqg(p, n_opt, members_per_opt, nominal, filter, x0_reg, ehat0, noise, rho, x_reg, u_reg,
-                                         xhat_reg, dist_out, meas_out, stats, est_stats, status, scratch, scratch_bytes);
+    return aoc64::api_track_ensemble_lqg("aoc_track_ensemble_lqg", p, n_opt, members_per_opt, nominal, filter, x0_reg, ehat0, noise,
+                                         rho, x_reg, u_reg, xhat_reg, dist_out, meas_out, stats, est_stats, status, scratch,
+                                         scratch_bytes);
+}
+
+size_t aoc_track_ensemble_lqg_limited_scratch_bytes(int32_t B, int32_t n_opt, int32_t T, int32_t members_per_opt,
+                                                    int32_t with_sat_count) {
+    return aoc64::track_ensemble_lqg_limited_scratch_bytes(B, n_opt, T, members_per_opt, with_sat_count);
+}
+
+int aoc_track_ensemble_lqg_limited(const aoc_problem* p, int32_t n_opt, int32_t members_per_opt, const double* nominal,
+                                   const double* filter, const double* x0_reg, const double* ehat0, const aoc_mpc_noise* noise,
+                                   const double* rho, const aoc_actuator_limits* limits, int32_t est_input, void* x_reg,
+                                   double* u_reg, double* xhat_reg, double* dist_out, double* meas_out, double* stats,
+                                   double* est_stats, double* sat, int32_t* sat_count, int32_t* status, void* scratch,
+                                   size_t scratch_bytes) {
+    return aoc64::api_track_ensemble_lqg("aoc_track_ensemble_lqg_limited", p, n_opt, members_per_opt, nominal, filter, x0_reg,
+                                         ehat0, noise, rho, x_reg, u_reg, xhat_reg, dist_out, meas_out, stats, est_stats, status,
+                                         scratch, scratch_bytes, true, limits, est_input, sat, sat_count);
 }
 
 size_t aoc_filter_gains_scratch_bytes(int32_t n_opt, int32_t T) { return aoc64::filter_gains_scratch_bytes(n_opt, T); }

@@ -22,7 +22,7 @@ namespace AOC_ARITH_NS {
 #endif  // AOC_KERNELS_ONLY
 #include "passes/ensemble.inc"   // kernel and launch function in one file (the latter uses make_const of api.inc)
 #include "passes/covariance.inc" // likewise (the nominal's record is that of ensemble.inc)
-#include "passes/lqg.inc"        // launch function only: k_cov_stage of covariance.inc, then the EST instance of ensemble.inc
+#include "passes/lqg.inc"        // launch function only: k_cov_stage of covariance.inc, then the EST (with limits: EST && LIM) instance of ensemble.inc
 #include "passes/filter.inc"     // the filter's gains: k_cov_stage without B K, then a chain kernel of its own
 #include "passes/lqgcov.inc"     // the joint (dx, e) prediction of the LQG loop: both k_cov_stage instances, then a chain kernel
 

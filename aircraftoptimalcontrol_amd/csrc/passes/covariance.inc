@@ -48,7 +48,9 @@ struct CovW { double w[6]; };   // sigma^2
 
 // BK = false (filter.inc): the record holds A_t instead of F_t — a filter knows its input — and the gains, which it does not
 // read, do not count as entries of the optimum's record.
-template <bool BK = true>
+// BENT = true (the limited LQG loop of lqg.inc, which never reads the record's copy of K): the two entries of B_t that depend
+// on the optimum, b20 and b50, lie where row 0 of that copy starts (COV_O_K, COV_O_K + 1); everything else is what it was.
+template <bool BK = true, bool BENT = false>
 __global__ __launch_bounds__(COV_THREADS) void k_cov_stage(KConst k, int n_opt, const real* __restrict__ nominal,
                                                            real* __restrict__ rec) {
     const int T = k.T;
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(COV_THREADS) void k_cov_stage(KConst k, int n_opt, 
 #pragma unroll
     for (int e = 0; e < 3; e++) out[COV_O_C / 2 + e] = real2v{xp[2 * e] - xnext[2 * e], xp[2 * e + 1] - xnext[2 * e + 1]};
 #pragma unroll
-    for (int e = 0; e < 6; e++) out[COV_O_K / 2 + e] = real2v{v[8 + 2 * e], v[9 + 2 * e]};
+    for (int e = 0; e < 6; e++) out[COV_O_K / 2 + e] = (BENT && e == 0) ? real2v{l.b20, l.b50} : real2v{v[8 + 2 * e], v[9 + 2 * e]};
     out[COV_O_FLAG / 2] = real2v{(real)flags, R(0.0)};
 }
 

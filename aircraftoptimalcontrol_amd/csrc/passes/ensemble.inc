@@ -159,6 +159,25 @@ struct EnsLim<true> {
     int* cnt;                  // [tile][T][2] or NULL
 };
 
+// ---- limits in the loop of the estimator (aoc_track_ensemble_lqg_limited) -------------------------------------------------
+// The EST && LIM instances cut the demand v_t = u_opt_t + K_t e^+_t as the LIM instances do.  The estimator's prediction
+// F_t e^+_t + c_t, F = A + B K, assumes the plant received v_t; one that is told the applied input u_t adds what the plant
+// got beside it, B_t (u_t - v_t).  B_t has the entries (2,0), (5,0) and (4,1): with g = u - v,
+//     e^-[2] += b20 g[0],   e^-[5] += b50 g[0],   e^-[4] += b41 g[1]       (a product and an addition each, two roundings)
+// where est_input says APPLIED and the sample is cut in at least one channel — a selection, so a sample that is not cut (and
+// every sample under infinite limits, or with est_input = DEMANDED) keeps the bits of the EST instance, a -0.0 included.
+// b20 and b50 depend on the optimum: k_cov_stage<true, true> (covariance.inc) writes them where the record's copy of K
+// starts (EST_O_B), which the estimator stages through LDS anyway and never reads; b41 is the model's.
+constexpr int EST_O_B = 42;     // where b20, b50 lie in a record of k_cov_stage<true, true> (COV_O_K, asserted in lqg.inc)
+
+// what the EST && LIM instances take beside EnsEst and EnsLim (nothing otherwise: those two keep their layout)
+template <bool ON>
+struct EnsEstLim {};
+template <>
+struct EnsEstLim<true> {
+    int applied;           // est_input == AOC_EST_INPUT_APPLIED
+};
+
 // max over |v| with a NaN that sticks (fmax would drop it): for non-negative doubles the IEEE order is the order of
 // the bit patterns as unsigned integers, and every NaN lies above +inf there
 __device__ __forceinline__ void ens_absmax(unsigned long long& m, double v) {
@@ -176,7 +195,8 @@ __device__ __forceinline__ bool ens_finite6(const real x[6]) {
 // ENV: also the per-tile envelope records part[tile][t][ENV_NREC] (above); every other output keeps its bits.
 // HIST: also the per-tile byte counts part[tile][t][HIST_NCH][HIST_NBIN] under `bins` (above); never together with ENV.
 // EST: the input is fed back from the estimate of `est` (above) instead of the true deviation; never with ENV or HIST.
-// LIM: the input is cut to the limits of `lim` (above), with sat and the cut counts; never with EST.
+// LIM: the input is cut to the limits of `lim` (above), with sat and the cut counts.
+// EST && LIM: the estimate's demand is cut, and the prediction is told the applied input where `esl` says so (above).
 template <bool WRITE, bool NOISE, typename XO, bool DIAG, bool ENV = false, bool HIST = false, bool EST = false,
           bool LIM = false>
 __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_per_opt, const real* __restrict__ nominal,
@@ -185,11 +205,10 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
                                                          real* __restrict__ stats, int* __restrict__ status,
                                                          real* __restrict__ part = nullptr,
                                                          const real* __restrict__ bins = nullptr, EnsEst<EST> est = {},
-                                                         EnsLim<LIM> lim = {}) {
+                                                         EnsLim<LIM> lim = {}, EnsEstLim<EST && LIM> esl = {}) {
 #pragma clang fp contract(off)
     static_assert(!(ENV && HIST), "the bins come from an envelope call: the two are never one instance");
     static_assert(!(EST && (ENV || HIST)), "the estimator instances reduce nothing over the members");
-    static_assert(!(EST && LIM), "the estimator predicts with F = A + B K: not the loop whose input is cut");
     __shared__ __attribute__((aligned(16))) real sh[2][ENS_BLK * ENS_REC];
     __shared__ __attribute__((aligned(16))) real ev[ENV ? ENV_S * ENV_ROWS * ENV_LD : 2];
     __shared__ __attribute__((aligned(16))) real hb[HIST ? 2 * ENS_BLK * HIST_REC : 2];
@@ -471,11 +490,13 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
         if constexpr (LIM) {
             const real v[2] = {u0, u1};
             real u[2];
+            bool any_cut = false;
 #pragma unroll
             for (int r = 0; r < 2; r++) {
                 const real dn = up[r] - ls[r], hn = up[r] + ls[r];
                 const real a = dn > llo[r] ? dn : llo[r], bb = hn < lhi[r] ? hn : lhi[r];
                 const bool cut = v[r] < a || v[r] > bb;
+                any_cut = any_cut || cut;
                 u[r] = v[r] < a ? a : (v[r] > bb ? bb : v[r]);
                 up[r] = u[r];
                 ncut[r] += cut ? 1 : 0;
@@ -485,6 +506,15 @@ __global__ __launch_bounds__(TILE) void k_track_ensemble(KConst kc, int tiles_pe
                 // here would cut the stage into blocks
                 const int n_cut = __popcll(__ballot(cut && in_B && first_bad > t));
                 cacc = lane == 2 * i + r ? n_cut : cacc;
+            }
+            if constexpr (EST) {   // e^-_{t+1} += B_t (u_t - v_t) where the estimator is told the applied input
+                const real2v bb = *(const real2v*)&ef[(t % ENS_BLK) * EST_FC + EST_O_B];   // every lane the same address
+                const real g0 = u[0] - v[0], g1 = u[1] - v[1];
+                const bool told = any_cut && esl.applied != 0;
+                const real c2 = eh[2] + bb.x * g0, c5 = eh[5] + bb.y * g0, c4 = eh[4] + k.b41 * g1;
+                eh[2] = told ? c2 : eh[2];
+                eh[5] = told ? c5 : eh[5];
+                eh[4] = told ? c4 : eh[4];
             }
             u0 = u[0];
             u1 = u[1];

@@ -9,7 +9,7 @@ JSON line.
                                              [--envelope FILE.npz] [--quantiles FILE.npz [--q 0.05 0.5 0.95]]
                                              [--predict FILE.npz] [--rho r0 r1 r2 r3 r4 r5 [--device-gains] [--measured c ...]
                                                                    [--predict-joint FILE.npz]]
-                                             [--u-min a b] [--u-max a b] [--u-rate a b]
+                                             [--u-min a b] [--u-max a b] [--u-rate a b] [--est-input applied|demanded]
 
 --envelope FILE.npz: also reduce over the members at every sample on the device (the tube around the optimum) and save
 n (T,), min_dx / max_dx (6,T), min_du / max_du (2,T), mean_dx (6,T), cov_dx (6,6,T), raw (T,44); the JSON line then
@@ -39,7 +39,12 @@ are then kept on the device to sample rms_dx (26 doubles per member and sample).
 member is cut to the range and, from sample 1 on, to within u-rate * dt of the input before (aoc_track_ensemble_limited);
 every other output is then that of the limited loop (--predict stays the prediction of the UNLIMITED linear loop).  The JSON
 line then carries "limits": the three pairs (null = unbounded), and "frac_cut": per channel the share of members cut at
-least once.  Not together with --rho.
+least once.  Together with --rho they need --est-input.
+--est-input applied | demanded (with --rho and a limit; aoc_track_ensemble_lqg_limited): the demand formed from the estimate is
+cut, and the estimator's prediction is told the applied input ("applied": it adds B_t (u_t - v_t) where a sample is cut) or
+left with its demand ("demanded": the estimator of --rho as it is, which a cut misleads).  The JSON line then carries
+"est_input" beside "limits", "frac_cut", "rho" and "rms_estimation_error".  --predict-joint stays the prediction of the loop
+WITHOUT limits.
 """
 import argparse
 import json
@@ -72,13 +77,19 @@ def main():
     ap.add_argument("--u-max", type=float, nargs=2, default=None, metavar=("THRUST", "MOMENT"), help="upper limit of the inputs")
     ap.add_argument("--u-rate", type=float, nargs=2, default=None, metavar=("THRUST", "MOMENT"),
                     help="largest change of the inputs per second")
+    ap.add_argument("--est-input", choices=("applied", "demanded"), default=None,
+                    help="with --rho and a limit: what the estimator's prediction is told")
     ap.add_argument("--q", type=float, nargs="+", default=[0.05, 0.5, 0.95], help="quantile levels of --quantiles")
     a = ap.parse_args()
     if a.rho is not None and (a.envelope or a.quantiles or a.predict):
         ap.error("--rho does not combine with --envelope, --quantiles or --predict")
     limits = {k: v for k, v in (("u_min", a.u_min), ("u_max", a.u_max), ("u_rate", a.u_rate)) if v is not None}
-    if limits and a.rho is not None:
-        ap.error("--u-min / --u-max / --u-rate do not combine with --rho (the estimator predicts with the uncut input)")
+    if limits and a.rho is not None and a.est_input is None:
+        ap.error("--u-min / --u-max / --u-rate combine with --rho only with --est-input applied | demanded (what the "
+                 "estimator's prediction is told once the input is cut)")
+    if a.est_input is not None and not (limits and a.rho is not None):
+        ap.error("--est-input goes with --rho and a limit (--u-min / --u-max / --u-rate)")
+    lqg_limits = dict(est_input=a.est_input, **limits) if a.est_input is not None else {}
     if a.predict_joint is not None and a.rho is None:
         ap.error("--predict-joint goes with --rho (the prediction of the loop with the estimator; --predict is the other one)")
     xx_opt = np.load(os.path.join(a.data, "xx_star.npy"))
@@ -91,11 +102,11 @@ def main():
     joint = dict(predict_joint=True, mean0=np.zeros(6), trajectories=True, to_host=False) if a.predict_joint is not None else {}
     if device_gains:
         r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, filter="device", rho=a.rho,
-                                 Sigma0=np.diag(np.asarray(a.delta) ** 2), measured=a.measured, **joint)
+                                 Sigma0=np.diag(np.asarray(a.delta) ** 2), measured=a.measured, **joint, **lqg_limits)
     elif a.rho is not None:
         L = batch.filter_gains(bp, xx_opt, uu_opt, np.diag(np.asarray(a.delta) ** 2), a.sigma, a.rho)[0]
         r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, filter=L, rho=a.rho,
-                                 Sigma0=np.diag(np.asarray(a.delta) ** 2) if joint else None, **joint)
+                                 Sigma0=np.diag(np.asarray(a.delta) ** 2) if joint else None, **joint, **lqg_limits)
     else:
         r = batch.track_ensemble(bp, xx_opt, uu_opt, delta=delta, sigma=a.sigma, seed=a.seed, envelope=a.envelope is not None,
                                  quantiles=a.q if a.quantiles is not None else None, predict=a.predict is not None,
@@ -109,6 +120,8 @@ def main():
         line.update(limits={k: finite(v) for k, v in r["limits"].items()}, frac_cut=sm["frac_cut"].tolist())
     if a.rho is not None:
         line.update(rho=list(a.rho), rms_estimation_error=np.sqrt(r["sum_e2"].mean(axis=0) / T).tolist())
+    if a.est_input is not None:
+        line.update(est_input=r["est_input"])
     if a.predict_joint is not None:
         pj = r["predicted_joint"][0]
         np.savez(a.predict_joint, status=r["predicted_joint_status"][0], **pj)

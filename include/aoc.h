@@ -72,7 +72,9 @@ extern "C" {
  *      (still 5, an addition: aoc_track_covariance_lqg, aoc_track_covariance_lqg_scratch_bytes — no struct, argument list or
  *      size query of an existing entry changed)
  *      (still 5, an addition: aoc_track_ensemble_limited, aoc_ensemble_limited_scratch_bytes, struct aoc_actuator_limits — no
- *      struct, argument list or size query of an existing entry changed) */
+ *      struct, argument list or size query of an existing entry changed)
+ *      (still 5, an addition: aoc_track_ensemble_lqg_limited, aoc_track_ensemble_lqg_limited_scratch_bytes,
+ *      AOC_EST_INPUT_* — no struct, argument list or size query of an existing entry changed) */
 #define AOC_ABI_VERSION 5
 
 #define AOC_TILE 64
@@ -637,8 +639,8 @@ int aoc_track_ensemble_histogram(const aoc_problem *prob, int32_t n_opt, int32_t
  * three; limits NULL; sat NULL; a NaN in lo, hi or rate; lo[r] > hi[r]; rate[r] <= 0.
  * The ensemble kernel (one more instance per mode; the arithmetic of a stage is shared), the mode's fold, and with sat_count
  * a fold of the tiles' counts.  No atomics.
- * Not covered: limits in the loop of aoc_track_ensemble_lqg (its estimator predicts with F = A + B K, which is wrong once the
- * input is cut), limits that vary with time or optimum, a rate limit at t = 0.
+ * Limits in the loop of aoc_track_ensemble_lqg are aoc_track_ensemble_lqg_limited (below).
+ * Not covered: limits that vary with time or optimum, a rate limit at t = 0.
  * --------------------------------------------------------------------------------------------- */
 #define AOC_SAT_NSTAT 6
 enum { AOC_ENS_MODE_STATS = 0, AOC_ENS_MODE_ENVELOPE = 1, AOC_ENS_MODE_HISTOGRAM = 2 };
@@ -727,6 +729,51 @@ int aoc_track_ensemble_lqg(const aoc_problem *prob, int32_t n_opt, int32_t membe
                            const double *rho, void *x_reg, double *u_reg, double *xhat_reg, double *dist_out,
                            double *meas_out, double *stats, double *est_stats, int32_t *status, void *scratch,
                            size_t scratch_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * That loop with the ACTUATOR LIMITS of aoc_track_ensemble_limited: noisy measurements, an estimate and a saturating actuator.
+ * For sample t = 0 .. T-2, with e^+_t as in aoc_track_ensemble_lqg and B_t the input Jacobian of Dynamics.step at
+ * (x_opt_t, u_opt_t),
+ *     v_t = u_opt_t + K_t e^+_t                                the demand, summed as in aoc_track_ensemble_lqg
+ *     u_t = v_t cut by the rule of aoc_track_ensemble_limited  the same selections; uprev = the APPLIED input, no rate limit at t = 0
+ *     x_{t+1} = Dynamics.step(x_t, u_t) + d_t
+ *     e^-_{t+1} = F_t e^+_t + c_t                              est_input = DEMANDED, or the sample is cut in neither channel
+ *     e^-_{t+1} = (F_t e^+_t + c_t) + B_t (u_t - v_t)          est_input = APPLIED and the sample is cut in a channel
+ * F = A + B K assumes the plant received the demand; an estimator that is told the applied input adds what the plant got beside
+ * it, and the separation of the linear loop is back: on a linear plant its error sequence is that of the loop without limits.
+ * B_t has the entries (2,0), (5,0) and (4,1): with g = u_t - v_t, rows 2 and 5 get b20 g[0] and b50 g[0], row 4 gets b41 g[1],
+ * each one product and one addition (two roundings).  The correction is a SELECTION on "cut in at least one channel": with
+ * infinite limits every output shared with aoc_track_ensemble_lqg has that call's bits (an estimate component of -0.0 included),
+ * for both values of est_input; so has, with est_input = DEMANDED and any limits, every member that is never cut.  A NaN demand
+ * stays NaN and is not cut.
+ * u_t is what the plant, the cost, statistics 6-7 and u_reg see, as in aoc_track_ensemble_limited.  est_stats, xhat_reg and
+ * meas_out are as in aoc_track_ensemble_lqg; sat and sat_count as in aoc_track_ensemble_limited (the count among the members
+ * with b < B and t < stats[15]).  Every other argument means what it means in aoc_track_ensemble_lqg.
+ * est_input: AOC_EST_INPUT_APPLIED (the estimator is told u_t) or AOC_EST_INPUT_DEMANDED (it is left with v_t: the estimator
+ *   of aoc_track_ensemble_lqg as it is, which a cut misleads).
+ * scratch: DEVICE, caller-owned, 16-byte aligned, at least
+ *   aoc_track_ensemble_lqg_limited_scratch_bytes(B, n_opt, T, members_per_opt, sat_count != NULL) bytes: what
+ *   aoc_track_ensemble_lqg takes, rounded up to 16, and 8 * T * ceil(B / 64) for the tiles' cut counts (0 for a geometry the
+ *   call refuses); the layout is private.  Nothing is allocated.
+ * AOC_EINVAL with the reason, before anything touches a device: the refusals of aoc_track_ensemble_lqg, in its order (scratch
+ * against this call's size); then limits NULL; sat NULL; a NaN in lo, hi or rate; lo[r] > hi[r]; rate[r] <= 0; est_input not
+ * one of the two.
+ * Kernels on prob->stream: the first kernel of aoc_track_covariance in a form that also leaves b20 and b50 in its record, the
+ * ensemble kernel (one more instance per form of aoc_track_ensemble_lqg; the arithmetic of a stage is shared), and with
+ * sat_count the fold of the tiles' counts.  No atomics.
+ * Not covered: the envelope or the histogram in this loop; a joint prediction of the limited loop (aoc_track_covariance_lqg
+ * describes the loop without limits); limits that vary with time or optimum; a rate limit at t = 0; filter gains that
+ * account for saturation.
+ * --------------------------------------------------------------------------------------------- */
+enum { AOC_EST_INPUT_DEMANDED = 0, AOC_EST_INPUT_APPLIED = 1 };
+size_t aoc_track_ensemble_lqg_limited_scratch_bytes(int32_t B, int32_t n_opt, int32_t T, int32_t members_per_opt,
+                                                    int32_t with_sat_count);
+int aoc_track_ensemble_lqg_limited(const aoc_problem *prob, int32_t n_opt, int32_t members_per_opt, const double *nominal,
+                                   const double *filter, const double *x0_reg, const double *ehat0,
+                                   const aoc_mpc_noise *noise, const double *rho, const aoc_actuator_limits *limits,
+                                   int32_t est_input, void *x_reg, double *u_reg, double *xhat_reg, double *dist_out,
+                                   double *meas_out, double *stats, double *est_stats, double *sat, int32_t *sat_count,
+                                   int32_t *status, void *scratch, size_t scratch_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * The GAINS of that Kalman filter, for every optimum at once: the filter Riccati recursion about the optimum, for the

@@ -2,7 +2,7 @@
 """Closed-loop tracking ensemble about ONE optimum: aoc_track_ensemble against the replicated path it replaces.
 
     python tools/ensemble_time.py [--members 65536 262144] [--T 1000] [--seconds 0.5] [--repeats 3] [--out FILE]
-                                  [--envelope] [--histogram] [--predict] [--lqg] [--filter] [--limits]
+                                  [--envelope] [--histogram] [--predict] [--lqg] [--filter] [--limits] [--lqg-limits]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/ensemble_time.py --trace --members N
     python tools/ensemble_time.py --kernel-times DIR                 (kernel times: a traced run of its own, then its summary)
 
@@ -63,6 +63,11 @@ the variants take turns inside each of --repeats rounds, so that a drift of the 
   M_inf      under infinite limits (the outputs of B_stats, bit for bit), no sat_count
   M_count    as M_fixed, with sat_count (the tiles' counts and their fold)
 and reports each over B_stats of the same run.
+--lqg-limits adds the estimator's loop with actuator limits (aoc_track_ensemble_lqg_limited, statistics only, the fixed limits
+of --limits, est_input = applied, no sat_count) beside the variants of --lqg, which it implies:
+  N_plain    no disturbance and no measurement noise drawn (against L_plain)
+  N_noise    both drawn on the device (against L_noise)
+and reports N_plain / L_plain and N_noise / L_noise of the same run.
 per size and variant the ms per call of every round, B/A, member-stages per second, and — from --valu, the vector
 instructions of one stage on the executed path of the ISA (tools/one_kernel.sh, tools/isa_loops.py) — the share of the fp64
 vector-issue roof (1024 SIMDs, one instruction per 4 cycles at 2.4 GHz): this kernel's bound is issue, not HBM.
@@ -84,7 +89,7 @@ DELTA_SCALE = np.array([0.3, 0.3, 0.5, 0.05, 0.1, 0.05])
 SIGMA = np.array([1e-3, 1e-3, 1e-2, 1e-4, 1e-3, 1e-4])
 
 
-def setup(B, T, g, envelope=False, histogram=False, lqg=False, limits=False):
+def setup(B, T, g, envelope=False, histogram=False, lqg=False, limits=False, lqg_limits=False):
     """Device buffers and the launch closures for B members."""
     import torch
     from aircraftoptimalcontrol_amd import _lib, batch
@@ -138,6 +143,21 @@ def setup(B, T, g, envelope=False, histogram=False, lqg=False, limits=False):
                   "aoc_track_ensemble_lqg")
 
         runs.update(L_plain=run_L, L_noise=lambda: run_L(noise=True))
+        if lqg_limits:
+            two = lambda a, b: (C.c_double * 2)(a, b)
+            lfixed = _lib.ActuatorLimits(two(-140.0, -260.0), two(360.0, 430.0), two(8200.0, 69000.0))
+            lsat = torch.empty((nt, batch.SAT_NSTAT, TILE), dtype=torch.float64, device=dev)
+            nlbytes = int(lib().aoc_track_ensemble_lqg_limited_scratch_bytes(B, 1, T, nt * TILE, 0))
+            assert nlbytes == nbytes
+
+            def run_N(noise=False):
+                check(lib().aoc_track_ensemble_lqg_limited(C.byref(pB), 1, nt * TILE, _ptr(nominal), _ptr(filt), _ptr(x0t), None,
+                                                           C.byref(nz) if noise else None, rho_c if noise else None,
+                                                           C.byref(lfixed), _lib.EST_INPUT_APPLIED, None, None, None, None, None,
+                                                           _ptr(stats), _ptr(est_stats), _ptr(lsat), None, _ptr(status),
+                                                           _ptr(scratch), nbytes), "aoc_track_ensemble_lqg_limited")
+
+            runs.update(N_plain=run_N, N_noise=lambda: run_N(noise=True))
     if limits:
         inf = float("inf")
         two = lambda a, b: (C.c_double * 2)(a, b)
@@ -547,6 +567,8 @@ def main():
     ap.add_argument("--filter", action="store_true", help="also time aoc_filter_gains for 1, 64 and 1024 optima")
     ap.add_argument("--joint", action="store_true", help="also time aoc_track_covariance_lqg for 1, 64 and 1024 optima")
     ap.add_argument("--limits", action="store_true", help="also time aoc_track_ensemble_limited, statistics only")
+    ap.add_argument("--lqg-limits", action="store_true",
+                    help="also time aoc_track_ensemble_lqg_limited against aoc_track_ensemble_lqg, statistics only")
     ap.add_argument("--hist-valu", type=int, default=0, help="vector instructions per stage of the histogram kernel (from the ISA)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -560,7 +582,7 @@ def main():
     for B in a.members:
         rec = dict(members=B)
         try:
-            runs = setup(B, a.T, g, a.envelope, a.histogram or a.predict, a.lqg, a.limits)
+            runs = setup(B, a.T, g, a.envelope, a.histogram or a.predict, a.lqg or a.lqg_limits, a.limits, a.lqg_limits)
             if a.predict:
                 if not a.histogram:       # the yardsticks of the prediction only, not the torch routes to the histogram
                     runs = {k: f for k, f in runs.items() if k in ("A", "B_stats", "B_noise", "B_env", "H", "L_plain", "L_noise", "M_fixed", "M_inf", "M_count")}
@@ -608,6 +630,13 @@ def main():
                                   B_noise_ms=med["B_noise"], L_noise_over_B_noise=round(med["L_noise"] / med["B_noise"], 4),
                                   L_plain_over_B_stats=round(med["L_plain"] / med["B_stats"], 4),
                                   spread_rel={k: sp(k) for k in ("L_plain", "L_noise", "B_stats", "B_noise")})
+            if a.lqg_limits:
+                sp = lambda k: round((max(ms[k]) - min(ms[k])) / med[k], 4)
+                ks = ("N_plain", "N_noise", "L_plain", "L_noise")
+                rec["lqg_limits"] = dict(**{k + "_ms": med[k] for k in ks},
+                                         N_plain_over_L_plain=round(med["N_plain"] / med["L_plain"], 4),
+                                         N_noise_over_L_noise=round(med["N_noise"] / med["L_noise"], 4),
+                                         spread_rel={k: sp(k) for k in ks})
             if a.limits:
                 sp = lambda k: round((max(ms[k]) - min(ms[k])) / med[k], 4)
                 ks = ("M_fixed", "M_inf", "M_count")
